@@ -11,8 +11,14 @@ the ones torch.distributed.run started (RANK / WORLD_SIZE in the environment) or
 N child processes this script starts itself BEFORE anything touches the GPU.  `value` = keyframe-iterations per second over
 all N GPUs.  Default workload: `1080p_3m` (3 M Gaussians at 1920x1080: the size north_star names, outside the 256 MiB
 Infinity Cache).
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  Everything else
+the line can carry -- roofline and per-kernel figures, step percentiles, the drop-in, extra workload and N > 1 configuration
+blocks, the CPU baseline -- is measured only with --full.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32, a fixed seeded sample of rows where an array is large; at most 64 MB in all).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -74,19 +80,27 @@ def parse_args():
     ap.add_argument("--graph", action="store_true", help="N=1 only: replay the step from a captured hipGraph -- raster mode: the resident "
                     "fwd+bwd; trainer / scaffold mode: the whole iteration (staging buffers for keyframe, target and learning rates). The "
                     "dominant kernel's HIP-event timing then comes from the profiled steps after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline, per-kernel and step-percentile figures, the drop-in "
+                         "and extra workload blocks, the N > 1 configurations (keyframe_parallel) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse the multi-rank path)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="all ranks use cuda:0 (with --backend gloo): exercises the N > 1 code path on a one-GPU box; not a measurement")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group and run the collectives even with one rank (exercises the RCCL calls on a one-GPU box)")
-    ap.add_argument("--breakdown", action="store_true", help="also print the per-kernel table to stderr")
+    ap.add_argument("--breakdown", action="store_true", help="also print the per-kernel table to stderr (its own profiled steps)")
     ap.add_argument("--fuse-projection", type=int, default=1, help="scaffold mode: 1 = the neural forward runs the rasterizer's per-Gaussian stage itself (SURVEY 8f n3)")
     ap.add_argument("--neural-flags", type=int, default=0, help="segs_neural_set_flags bits for A/B profiles (1 = SEGS_NEURAL_ONE_KERNEL_BACKWARD)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extra blocks of the line (mapper_step, config3, render_only_ms): A/B runs and profiles")
-    return ap.parse_args()
+                    help="--full: skip the untimed extra blocks of the line (mapper_step, config3, render_only_ms): A/B runs and profiles")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(n: int) -> int:
@@ -138,7 +152,7 @@ def main():
 
     # The C++ drop-in path (libgaussian_rasterizer.so -> libcuda_rasterizer.so -> C ABI) is timed by its own driver in a child
     # process that has finished before this process touches the GPU.
-    want_extras = args.gpus == 1 and args.mode == "raster" and not args.no_extras and "WORLD_SIZE" not in os.environ
+    want_extras = args.full and args.gpus == 1 and args.mode == "raster" and not args.no_extras and "WORLD_SIZE" not in os.environ
     sc0 = scenes.make_config_scene(args.workload, keyframe=0) if want_extras else None
     cpp_dropin = cpp_dropin_block(sc0) if want_extras else None
 
@@ -177,6 +191,8 @@ def main():
     bg, m3, col, op, sca, rot = t(sc.bg), t(sc.means3D), t(sc.colors), t(sc.opacity), t(sc.scales), t(sc.rotations)
     view, proj, campos = t(cam.world_view_transform), t(cam.full_proj_transform), t(cam.camera_center)
     dL = t(sc.dL_dout_color)
+    # the training targets are seeded too: with the same arguments every run trains on the same inputs
+    target_gen = torch.Generator(device=dev).manual_seed(0x5E65 + rank)
     tstep = None
     if args.mode == "scaffold":
         from segs_slam_amd import neural_gaussians as ng
@@ -188,14 +204,14 @@ def main():
         tstep.single_rank_collectives = args.force_dist
         eng = tstep.engine
         kfs = [ng.Keyframe(view, proj, campos, torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], device=dev), cam.tanfovx, cam.tanfovy)]
-        gts = [torch.rand(3, cam.height, cam.width, device=dev)]
+        gts = [torch.rand(3, cam.height, cam.width, device=dev, generator=target_gen)]
         tstep.keyframe_for = lambda step, n: 0
     elif args.mode == "trainer":
         from segs_slam_amd.gaussian_trainer import TrainerStep, keyframe_tensors
         tstep = TrainerStep.on_gpu(sc, dev, sharded_optimizer=sharded_opt, single_rank_collectives=args.force_dist)
         eng = tstep.engine
         kfs = [keyframe_tensors(cam, dev)]
-        gts = [torch.rand(3, cam.height, cam.width, device=dev)]
+        gts = [torch.rand(3, cam.height, cam.width, device=dev, generator=target_gen)]
         tstep.keyframe_for = lambda step, n: 0
     else:
         eng = RasterEngine(sc.P, cam.width, cam.height, dev, resident=not args.sync_forward)
@@ -210,9 +226,11 @@ def main():
                                    single_rank_collectives=args.force_dist, grads=eng.grads_flat)
         raster_params = torch.zeros_like(eng.grads_flat) if raster_ex.sharded else None
 
+    last_loss = [None]      # what training_once handed back in the latest step (--dump-outputs)
+
     def step():
         if tstep is not None:
-            tstep.training_once(kfs, gts)
+            last_loss[0] = tstep.training_once(kfs, gts)
             return
         eng.forward(bg, m3, col, op, sca, rot, view, proj, campos, cam.tanfovx, cam.tanfovy)
         eng.backward(dL)
@@ -252,41 +270,55 @@ def main():
             step()
         torch.cuda.synchronize()
     fence()
-    step_events = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # one record per step: p10 / p50 / p90
-    with KernelProfile(LIVE_EVENT_KERNELS if (graph is None and not step_graph) else []) as prof_live:
+    # --full only: one HIP event per step (p10 / p50 / p90) and the live tile-kernel events; a plain run times the steps alone
+    step_events = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
+    live_ctx = KernelProfile(LIVE_EVENT_KERNELS if (graph is None and not step_graph) else []) if args.full else contextlib.nullcontext()
+    with live_ctx as prof_live:
         t0 = time.perf_counter()
-        step_events[0].record()
+        if step_events:
+            step_events[0].record()
         for i in range(args.steps):
             if graph is not None:
                 graph.replay()
             else:
                 step()
-            step_events[i + 1].record()
+            if step_events:
+                step_events[i + 1].record()
         fence()
         elapsed = time.perf_counter() - t0
-    per_step_ms = sorted(step_events[i].elapsed_time(step_events[i + 1]) for i in range(args.steps))
+    per_step_ms = sorted(step_events[i].elapsed_time(step_events[i + 1]) for i in range(args.steps)) if step_events else None
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-
-    # ---- per-kernel table: the same steady-state steps once more, every kernel bracketed by HIP events (not in the timed
-    # region: two event records per kernel would perturb it)
-    n_prof = max(1, min(args.steps, 20))
     replays = getattr(tstep, "graph_replays", 0) if step_graph else 0
-    if step_graph:
-        tstep.enable_graph(False)      # the per-kernel table needs the eager launches (events cannot go inside a replay)
-    with KernelProfile() as prof_all:
-        for _ in range(n_prof):
-            step()
-        torch.cuda.synchronize()
-    breakdown = prof_all.result
-    per_step = {k: v["total_ms"] / n_prof for k, v in breakdown.items()}
-    dominant = max((k for k in per_step if k != "memset"), key=lambda k: per_step[k])
+
+    if args.dump_outputs:
+        # the last timed step as its caller would see it: a dropped training step is run again first (finish(), every rank)
+        if tstep is not None:
+            tstep.finish()
+        if rank == 0:
+            eng.check(raise_on_overflow=args.mode == "raster")
+            dump_outputs(args.dump_outputs, args.mode, eng, tstep, last_loss[0])
+
+    # ---- per-kernel table (--full, --breakdown): the same steady-state steps once more, every kernel bracketed by HIP events
+    # (not in the timed region: two event records per kernel would perturb it)
+    per_kernel = args.full or args.breakdown
+    n_prof = max(1, min(args.steps, 20))
+    if per_kernel:
+        if step_graph:
+            tstep.enable_graph(False)      # the per-kernel table needs the eager launches (events cannot go inside a replay)
+        with KernelProfile() as prof_all:
+            for _ in range(n_prof):
+                step()
+            torch.cuda.synchronize()
+        breakdown = prof_all.result
+        per_step = {k: v["total_ms"] / n_prof for k, v in breakdown.items()}
+        dominant = max((k for k in per_step if k != "memset"), key=lambda k: per_step[k])
     sort_names = ("radix_count_kernel", "radix_scan_kernel", "radix_scatter_kernel")
 
     dist_extra = None
-    if use_dist and args.mode == "raster" and not args.no_extras:
+    if args.full and use_dist and args.mode == "raster" and not args.no_extras:
         try:
             dist_extra = dist_blocks(world, rank, dev, sharded_opt, args.force_dist)
         except Exception as e:  # noqa: BLE001  (every rank takes the same path: a failure is one of construction, not of one rank)
@@ -303,24 +335,7 @@ def main():
         R_ref = eng.R_reference or eng.R
         R_live = getattr(eng, "R_live", 0) or eng.R
         P_vis = int((eng.radii > 0).sum().item())
-        gx, gy = (cam.width + 15) // 16, (cam.height + 15) // 16
-        passes_tile = (max(1, int(gx * gy - 1).bit_length()) + 7) // 8
-        passes = int(round(breakdown.get("radix_scatter_kernel", {"launches": 0})["launches"] / n_prof))
-        passes_depth = max(passes - passes_tile, 0)
-        ab_ref = algorithmic_bytes(eng.P_active, P_vis, R_ref, cam.width, cam.height, passes_depth, passes_tile)
-        ab_live = algorithmic_bytes(eng.P_active, P_vis, R_live, cam.width, cam.height, passes_depth, passes_tile)
-        live = prof_live.result.get(dominant)
-        dom = live if live else breakdown[dominant]
-        dom_src = "HIP events inside the timed region" if live else f"HIP events over {n_prof} steady-state steps after the timed region"
-
-        def dom_bytes(ab):
-            return ab[dominant] if dominant in ab else ab["radix_sort(all passes)"] / (3 * max(passes, 1))
-        t_dom = dom["avg_ms"] * 1e-3
-        achieved = dom_bytes(ab_live) / t_dom / 1e9
-        pmc, pmc_src = pmc_entry(args.workload, dominant) if args.mode == "raster" else (None, None)
-        total_bytes = sum(ab_ref.values())
         ms_per_step = elapsed / args.steps * 1e3
-        raster_ms = sum(per_step.values())
         out = {
             "metric": "mapper train-iters/sec (fwd+bwd raster)",
             "value": world * args.steps / elapsed,
@@ -345,73 +360,131 @@ def main():
                                    + ((", dense all-reduce" if not tstep._exchange_sharded() else ", reduce-scatter -> sharded Adam -> all-gather")
                                       if (world > 1 and tstep is not None) else ""),
                        "P": eng.P_active, "P_visible": P_vis, "num_rendered": R_ref, "instances_binned": eng.R, "instances_live": R_live,
-                       "width": cam.width, "height": cam.height,
-                       "sort_passes": {"depth_keys_P": passes_depth, "tile_keys_R": passes_tile}, "parallelism": f"keyframe-dp{world}",
+                       "width": cam.width, "height": cam.height, "parallelism": f"keyframe-dp{world}",
                        "forward": "sync (reference API)" if args.sync_forward else "resident (no host sync)",
                        "hipgraph": (f"whole iteration replayed from a captured hipGraph ({replays} replays)" if step_graph else
                                     ("resident fwd+bwd replayed from a captured hipGraph" if graph is not None else "off"))},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc.get("hbm_bytes") if pmc else None, "traffic_source": pmc_src,
-                         "traffic_stale": pmc.get("stale") if pmc else None,
-                         "algorithmic_bytes_per_launch": dom_bytes(ab_live), "priced_on": "instances_live (what the launch walks)",
-                         "avg_launch_ms": dom["avg_ms"], "launches": dom["launches"], "timing": dom_src,
-                         "on_reference_num_rendered": {"algorithmic_bytes_per_launch": dom_bytes(ab_ref),
-                                                       "achieved": dom_bytes(ab_ref) / t_dom / 1e9,
-                                                       "frac": dom_bytes(ab_ref) / t_dom / 1e9 / HBM_PEAK_GBPS},
-                         "note": "the tile kernels are VALU-/atomic-bound, not HBM-bound (SURVEY 8d): see roofline_valu, roofline_atomic"},
-            "roofline_valu": None, "roofline_atomic": None,
-            "raster": {"algorithmic_bytes": total_bytes, "algorithmic_bytes_live": sum(ab_live.values()), "kernel_ms_sum": raster_ms,
-                       "kernel_ms_source": f"HIP events over {n_prof} steady-state steps after the timed region",
-                       "achieved_GBps": total_bytes / (raster_ms * 1e-3) / 1e9,
-                       "whole_step_GBps": total_bytes / (ms_per_step * 1e-3) / 1e9,
-                       "whole_step_frac_of_hbm_peak": total_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                       "kernel_ms": {k: round(v, 4) for k, v in sorted(per_step.items(), key=lambda kv: -kv[1])},
-                       "radix_sort_ms": round(sum(per_step.get(k, 0.0) for k in sort_names), 4)},
         }
-        if pmc and "SQ_INSTS_VALU" in pmc:
-            a = pmc["SQ_INSTS_VALU"] / t_dom / 1e9
-            out["roofline_valu"] = {"bound": "valu", "kernel": dominant, "achieved": a, "peak": VALU_PEAK_GINST,
-                                    "unit": "G wave-instructions/s", "frac": a / VALU_PEAK_GINST,
-                                    "wave_instructions_per_launch": pmc["SQ_INSTS_VALU"], "source": pmc_src, "stale": pmc.get("stale"),
-                                    "note": "SQ_INSTS_VALU per launch / launch time against 1024 SIMDs x 2.4 GHz / 2 cycles per "
-                                            "wave64 instruction; v_exp/v_rcp/permlane take 8 and v_cndmask/v_cmp/DPP 4 cycles"}
-        if pmc and "write_bytes" in pmc:
-            a = pmc["write_bytes"] / t_dom / 1e9
-            out["roofline_atomic"] = {"bound": "global float atomics", "kernel": dominant, "achieved": a, "peak": ATOMIC_PEAK_GBPS,
-                                      "unit": "GB/s", "frac": a / ATOMIC_PEAK_GBPS, "write_bytes_per_launch": pmc["write_bytes"],
-                                      "algorithmic_atomic_bytes": 36 * R_live, "source": pmc_src, "stale": pmc.get("stale")}
-        try:   # the tile kernels are reported in (pixel, Gaussian) pairs per second next to the byte figure
-            out["raster"].update(pair_rates(eng, cam, per_step))
-        except Exception as e:  # noqa: BLE001  (measurement garnish only; never fail the bench line over it)
-            out["raster"]["pairs_error"] = str(e)
-        pct = lambda q: per_step_ms[min(len(per_step_ms) - 1, int(q * len(per_step_ms)))]  # noqa: E731
-        out["step_ms"] = {"p10": pct(0.10), "p50": pct(0.50), "p90": pct(0.90), "min": per_step_ms[0], "max": per_step_ms[-1],
-                          "source": "one HIP event per step on the launch stream, inside the timed region (device time between "
-                                    "step ends; the line's ms_per_step is the host clock over all K steps)"}
-        if world == 1 and args.mode == "raster" and not args.no_extras:
-            try:
-                out["dropin"] = dropin_block(sc, cpp_dropin, world * args.steps / elapsed)
-            except Exception as e:  # noqa: BLE001  (extra blocks never fail the bench line)
-                out["dropin"] = {"error": f"{type(e).__name__}: {e}"}
-            extras = [("render_only_ms", lambda: render_only(eng, (bg, m3, col, op, sca, rot, view, proj, campos, cam.tanfovx, cam.tanfovy))),
-                      ("mapper_step", lambda: mapper_step_block(dev)), ("replica_step", lambda: replica_step_block(dev)),
-                      ("config3", lambda: config3_block(dev)),
-                      ("config3_reference_schedule", lambda: config3_reference_schedule_block(dev))]
-            for key, fn in extras:
+        if args.full:
+            gx, gy = (cam.width + 15) // 16, (cam.height + 15) // 16
+            passes_tile = (max(1, int(gx * gy - 1).bit_length()) + 7) // 8
+            passes = int(round(breakdown.get("radix_scatter_kernel", {"launches": 0})["launches"] / n_prof))
+            passes_depth = max(passes - passes_tile, 0)
+            ab_ref = algorithmic_bytes(eng.P_active, P_vis, R_ref, cam.width, cam.height, passes_depth, passes_tile)
+            ab_live = algorithmic_bytes(eng.P_active, P_vis, R_live, cam.width, cam.height, passes_depth, passes_tile)
+            live = prof_live.result.get(dominant)
+            dom = live if live else breakdown[dominant]
+            dom_src = "HIP events inside the timed region" if live else f"HIP events over {n_prof} steady-state steps after the timed region"
+
+            def dom_bytes(ab):
+                return ab[dominant] if dominant in ab else ab["radix_sort(all passes)"] / (3 * max(passes, 1))
+            t_dom = dom["avg_ms"] * 1e-3
+            achieved = dom_bytes(ab_live) / t_dom / 1e9
+            pmc, pmc_src = pmc_entry(args.workload, dominant) if args.mode == "raster" else (None, None)
+            total_bytes = sum(ab_ref.values())
+            raster_ms = sum(per_step.values())
+            out["config"]["sort_passes"] = {"depth_keys_P": passes_depth, "tile_keys_R": passes_tile}
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc.get("hbm_bytes") if pmc else None, "traffic_source": pmc_src,
+                             "traffic_stale": pmc.get("stale") if pmc else None,
+                             "algorithmic_bytes_per_launch": dom_bytes(ab_live), "priced_on": "instances_live (what the launch walks)",
+                             "avg_launch_ms": dom["avg_ms"], "launches": dom["launches"], "timing": dom_src,
+                             "on_reference_num_rendered": {"algorithmic_bytes_per_launch": dom_bytes(ab_ref),
+                                                           "achieved": dom_bytes(ab_ref) / t_dom / 1e9,
+                                                           "frac": dom_bytes(ab_ref) / t_dom / 1e9 / HBM_PEAK_GBPS},
+                             "note": "the tile kernels are VALU-/atomic-bound, not HBM-bound (SURVEY 8d): see roofline_valu, roofline_atomic"},
+                "roofline_valu": None, "roofline_atomic": None,
+                "raster": {"algorithmic_bytes": total_bytes, "algorithmic_bytes_live": sum(ab_live.values()), "kernel_ms_sum": raster_ms,
+                           "kernel_ms_source": f"HIP events over {n_prof} steady-state steps after the timed region",
+                           "achieved_GBps": total_bytes / (raster_ms * 1e-3) / 1e9,
+                           "whole_step_GBps": total_bytes / (ms_per_step * 1e-3) / 1e9,
+                           "whole_step_frac_of_hbm_peak": total_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                           "kernel_ms": {k: round(v, 4) for k, v in sorted(per_step.items(), key=lambda kv: -kv[1])},
+                           "radix_sort_ms": round(sum(per_step.get(k, 0.0) for k in sort_names), 4)},
+            })
+            if pmc and "SQ_INSTS_VALU" in pmc:
+                a = pmc["SQ_INSTS_VALU"] / t_dom / 1e9
+                out["roofline_valu"] = {"bound": "valu", "kernel": dominant, "achieved": a, "peak": VALU_PEAK_GINST,
+                                        "unit": "G wave-instructions/s", "frac": a / VALU_PEAK_GINST,
+                                        "wave_instructions_per_launch": pmc["SQ_INSTS_VALU"], "source": pmc_src, "stale": pmc.get("stale"),
+                                        "note": "SQ_INSTS_VALU per launch / launch time against 1024 SIMDs x 2.4 GHz / 2 cycles per "
+                                                "wave64 instruction; v_exp/v_rcp/permlane take 8 and v_cndmask/v_cmp/DPP 4 cycles"}
+            if pmc and "write_bytes" in pmc:
+                a = pmc["write_bytes"] / t_dom / 1e9
+                out["roofline_atomic"] = {"bound": "global float atomics", "kernel": dominant, "achieved": a, "peak": ATOMIC_PEAK_GBPS,
+                                          "unit": "GB/s", "frac": a / ATOMIC_PEAK_GBPS, "write_bytes_per_launch": pmc["write_bytes"],
+                                          "algorithmic_atomic_bytes": 36 * R_live, "source": pmc_src, "stale": pmc.get("stale")}
+            try:   # the tile kernels are reported in (pixel, Gaussian) pairs per second next to the byte figure
+                out["raster"].update(pair_rates(eng, cam, per_step))
+            except Exception as e:  # noqa: BLE001  (measurement garnish only; never fail the bench line over it)
+                out["raster"]["pairs_error"] = str(e)
+            pct = lambda q: per_step_ms[min(len(per_step_ms) - 1, int(q * len(per_step_ms)))]  # noqa: E731
+            out["step_ms"] = {"p10": pct(0.10), "p50": pct(0.50), "p90": pct(0.90), "min": per_step_ms[0], "max": per_step_ms[-1],
+                              "source": "one HIP event per step on the launch stream, inside the timed region (device time between "
+                                        "step ends; the line's ms_per_step is the host clock over all K steps)"}
+            if world == 1 and args.mode == "raster" and not args.no_extras:
                 try:
-                    out[key] = fn()
+                    out["dropin"] = dropin_block(sc, cpp_dropin, world * args.steps / elapsed)
                 except Exception as e:  # noqa: BLE001  (extra blocks never fail the bench line)
-                    out[key] = {"error": f"{type(e).__name__}: {e}"}
-        if dist_extra is not None:
-            out["keyframe_parallel"] = dist_extra
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(sc)
+                    out["dropin"] = {"error": f"{type(e).__name__}: {e}"}
+                extras = [("render_only_ms", lambda: render_only(eng, (bg, m3, col, op, sca, rot, view, proj, campos, cam.tanfovx, cam.tanfovy))),
+                          ("mapper_step", lambda: mapper_step_block(dev)), ("replica_step", lambda: replica_step_block(dev)),
+                          ("config3", lambda: config3_block(dev)),
+                          ("config3_reference_schedule", lambda: config3_reference_schedule_block(dev))]
+                for key, fn in extras:
+                    try:
+                        out[key] = fn()
+                    except Exception as e:  # noqa: BLE001  (extra blocks never fail the bench line)
+                        out[key] = {"error": f"{type(e).__name__}: {e}"}
+            if dist_extra is not None:
+                out["keyframe_parallel"] = dist_extra
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(sc)
         if args.breakdown:
             for k, v in sorted(per_step.items(), key=lambda kv: -kv[1]):
                 print(f"  {k:32s} {v:8.4f} ms/step", file=sys.stderr)
         print(json.dumps(out), file=json_out, flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, mode, eng, tstep, loss, rows: int = 1 << 17, seed: int = 0x5E65):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy.  raster mode: the image, the
+    radii, dL/dmean2D and the parameter gradients (after the exchange when N > 1); trainer / scaffold mode: the loss, the image
+    and the parameters after the optimizer step.  Arrays of more than `rows` rows (Gaussians, or elements of the flat scaffold
+    parameter buffer) are cut to one fixed, seeded sample of rows, written as `<kind>_rows.npy` (float64); at most 64 MB in all."""
+    import numpy as np
+    import torch
+    image = (tstep.engine if tstep is not None else eng).out_color
+    arrays = {"image": image}
+    if loss is not None:
+        arrays["loss"] = torch.as_tensor(loss, dtype=torch.float32).reshape(1)
+    if mode == "raster":
+        P = eng.P_active
+        per_row = {"radii": eng.radii[:P], "dL_dmean2D": eng.dL_dmean2D[:P]}
+        per_row.update({"dL_d" + k: v[:P] for k, v in eng.grads.items()})
+        kind, n = "gaussian", P
+    elif mode == "trainer":
+        per_row, kind, n = dict(tstep.params), "gaussian", tstep.P
+    else:
+        per_row, kind, n = {"params": tstep.model.params}, "param", tstep.model.params.numel()
+    if n > rows:
+        idx = np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+        sel = torch.from_numpy(idx).to(image.device)
+        per_row = {k: v.index_select(0, sel) for k, v in per_row.items()}
+        arrays[f"{kind}_rows"] = idx.astype(np.float64)
+    arrays.update(per_row)
+    host = {k: (v if isinstance(v, np.ndarray) else v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def cpp_dropin_block(sc, steps: int = 50, warmup: int = 10):

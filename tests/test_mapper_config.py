@@ -1,5 +1,5 @@
 """segs_slam_amd.mapper_config: the reference's OpenCV-FileStorage YAML configuration (src/gaussian_mapper.cpp:224-520)."""
-import glob
+import json
 import os
 
 import numpy as np
@@ -100,21 +100,30 @@ def test_rejects_what_the_format_does_not_contain(tmp_path):
         mc.load_mapper_config(_write(tmp_path, "%YAML:1.0\nModel.feat_dim: thirty-two\n"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/cfg/gaussian_mapper"), reason="reference tree not present")
-def test_every_shipped_configuration_parses():
-    files = sorted(glob.glob("/root/reference/cfg/gaussian_mapper/**/*.yaml", recursive=True))
-    assert len(files) > 10
+# the key -> value content of every configuration file the reference ships (tests/golden/make_cfg_values_golden.py)
+SHIPPED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mapper_cfg_values.json")
+
+
+def test_every_shipped_configuration_parses(tmp_path):
+    """Every shipped configuration, written back in the file format from the committed extract of its values, reads back to
+    the same values and maps to a consistent typed configuration."""
+    with open(SHIPPED) as f:
+        shipped = json.load(f)
+    assert len(shipped) > 10
     anchor_cfgs = 0
-    for f in files:
-        cfg = mc.load_mapper_config(f)
+    for rel, values in sorted(shipped.items()):
+        path = tmp_path / rel.replace("/", "__")
+        path.write_text("%YAML:1.0\n" + "".join(f"{k}: {v!r}  # {rel}\n" for k, v in values.items()), encoding="utf-8")
+        cfg = mc.load_mapper_config(str(path))
+        assert cfg.raw == values, rel
         if "Model.feat_dim" not in cfg.raw:      # files inherited from Photo-SLAM without the anchor keys (e.g. Monocular/ETH3D)
             assert cfg.model.feat_dim == 0
             continue
         anchor_cfgs += 1
-        assert cfg.model.feat_dim == 32 and cfg.model.n_offsets == 10, f      # what csrc/neural.hip is compiled for
-        assert cfg.opt.lambda_dssim > 0 and cfg.densify.update_interval > 0, f
+        assert cfg.model.feat_dim == 32 and cfg.model.n_offsets == 10, rel    # what csrc/neural.hip is compiled for
+        assert cfg.opt.lambda_dssim > 0 and cfg.densify.update_interval > 0, rel
     assert anchor_cfgs > 10
-    cfg = mc.load_mapper_config("/root/reference/cfg/gaussian_mapper/RGB-D/Replica/office0.yaml")
+    cfg = mc.mapper_config_from_values(shipped["cfg/gaussian_mapper/RGB-D/Replica/office0.yaml"])
     assert cfg.model.appearance_dim == 32 and cfg.model.use_feat_bank and cfg.opt.offset_lr_init == 0.08
     assert (cfg.densify.start_stat, cfg.densify.update_from, cfg.densify.update_until) == (500, 1500, 25500)
     assert cfg.use_frequency_regularization and cfg.scale_num == 3 and cfg.lambda_frequency_high == 0.01

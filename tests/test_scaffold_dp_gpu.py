@@ -6,7 +6,8 @@ reduce-scatter -> Adam on the rank's shard -> all-gather) and the fused Adam app
     (SURVEY 8e: parity at gradient level; float atomics in the raster backward sum in arbitrary order -> 1e-4 relative);
   * the parameter UPDATE after two steps agrees with the single-process one to 2e-3 relative wherever both steps'
     gradients are more than rounding noise (Adam with eps 1e-15 turns a gradient that is itself noise into a full-size
-    step of either sign, so entries below 1e-6 of the largest gradient are left out);
+    step of either sign, so entries below 1e-6 of the largest gradient are left out, and the bound on the worst entry holds
+    above 1e-5, clear of the run-to-run noise of the second step's gradients);
   * through an adjust_anchor iteration the ranks grow and prune the SAME map: the four densification statistics are
     accumulated per rank and summed over ranks right before adjust_anchor (src/gaussian_model.cpp:1459-1503, 1701-1762),
     anchors / parameters / statistics / Adam step counts are bit-identical on both ranks afterwards, and the summed
@@ -104,7 +105,14 @@ def test_two_rank_scaffold_step_matches_single_process_mean_gradient(single_proc
     upd, upd_ref = (p0 - p_init)[solid], (ref - p_init)[solid]
     err = np.abs(upd - upd_ref)
     bad = err > 2e-3 * np.abs(upd_ref) + 1e-7          # (a handful of entries sit where Adam's normalisation is steep)
-    assert bad.mean() < 1e-4 and err.max() < 5e-3 * np.abs(upd_ref).max(), (float(bad.mean()), float(err.max()), float(np.abs(upd_ref).max()))
+    # the worst entry is bounded where both gradients clear 1e-5 of the largest: two runs of the SAME single-process step differ
+    # in their second-step gradients by up to ~3.5e-6 of the largest (float atomics in the raster backward; an entry whose first
+    # gradient is noise takes a full Adam step of either sign and moves its neighbours' next gradients), so an entry just above
+    # 1e-6 can change its two-step update by a whole learning-rate step between runs
+    firm = ((np.abs(g_one[0]) > 1e-5 * np.abs(g_one[0]).max()) & (np.abs(g_one[1]) > 1e-5 * np.abs(g_one[1]).max()))[solid]
+    assert firm.mean() > 0.5, float(firm.mean())
+    worst = float(err[firm].max())
+    assert bad.mean() < 1e-4 and worst < 5e-3 * np.abs(upd_ref).max(), (float(bad.mean()), worst, float(np.abs(upd_ref).max()))
     # nothing anywhere moved by more than two full-size steps
     assert np.abs(p0 - ref).max() <= 4 * 0.08, float(np.abs(p0 - ref).max())
 

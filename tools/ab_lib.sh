@@ -14,6 +14,6 @@ line() { python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['raster']['kernel_ms']
 print('$1', round(d['value'],1), round(d['ms_per_step'],4), {a: k[a] for a in sorted(k)})"; }
 for i in 1 2; do
-  (cd "$ROOT" && python3 bench.py --no-extras --no-cpu-baseline --breakdown "$@" 2>/dev/null | line "tree ")
-  (cd "$ROOT" && SEGS_RASTER_LIB="$TMP/tree/segs-slam_amd/csrc/libsegs_raster.so" python3 bench.py --no-extras --no-cpu-baseline --breakdown "$@" 2>/dev/null | line "other")
+  (cd "$ROOT" && python3 bench.py --no-extras --no-cpu-baseline --breakdown --full "$@" 2>/dev/null | line "tree ")
+  (cd "$ROOT" && SEGS_RASTER_LIB="$TMP/tree/segs-slam_amd/csrc/libsegs_raster.so" python3 bench.py --no-extras --no-cpu-baseline --breakdown --full "$@" 2>/dev/null | line "other")
 done

@@ -8,7 +8,7 @@ print('$1', 'it/s', round(d['value'],1), 'ms', round(d['ms_per_step'],4), 'bwd',
 for wl in $1; do
   echo "== $wl"
   for i in $(seq 1 ${2:-2}); do
-    SEGS_RENDER_BWD_MFMA=1 python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | line "mfma"
-    python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | line "valu"
+    SEGS_RENDER_BWD_MFMA=1 python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras --full 2>/dev/null | line "mfma"
+    python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras --full 2>/dev/null | line "valu"
   done
 done

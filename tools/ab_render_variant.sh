@@ -17,7 +17,7 @@ print('$1', 'it/s', round(d['value'],1), 'ms', round(d['ms_per_step'],4), 'bwd',
 for wl in $WLS; do
   echo "== $wl  variant: $ENVS $*"
   for i in 1 2; do
-    python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | line "tree   "
-    env $ENVS SEGS_RASTER_LIB="$TMP/libsegs_variant.so" python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | line "variant"
+    python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras --full 2>/dev/null | line "tree   "
+    env $ENVS SEGS_RASTER_LIB="$TMP/libsegs_variant.so" python3 bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras --full 2>/dev/null | line "variant"
   done
 done

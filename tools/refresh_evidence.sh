@@ -7,7 +7,7 @@ tools/collect_profiles.sh $TAG c2_1080p
 OUT=gpurun_out/${TAG}_other_workloads.txt
 : > $OUT
 for WL in c1 c2 1080p_1m 1080p_2m 1080p_3m c5; do
-  timeout -k 10 300 python3 bench.py --workload $WL --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --workload $WL --no-cpu-baseline --full 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('$WL', round(d['value'], 1), round(d['ms_per_step'], 4), d['config']['num_rendered'], round(d['roofline']['avg_launch_ms'], 4), round(d['raster']['achieved_GBps'], 1))" >> $OUT
@@ -15,13 +15,13 @@ print('$WL', round(d['value'], 1), round(d['ms_per_step'], 4), d['config']['num_
 done
 for M in "trainer c2_1080p" "trainer c4" "scaffold c2_1080p" "scaffold c2"; do
   set -- $M
-  timeout -k 10 300 python3 bench.py --mode $1 --workload $2 --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --mode $1 --workload $2 --no-cpu-baseline --full 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('$1', '$2', round(d['value'], 1), round(d['ms_per_step'], 4), d['config']['num_rendered'])" >> $OUT
   echo "$M done"
 done
-timeout -k 10 300 python3 bench.py --mode scaffold --workload c5 --anchors 300000 --no-cpu-baseline 2>/dev/null | python3 -c "
+timeout -k 10 300 python3 bench.py --mode scaffold --workload c5 --anchors 300000 --no-cpu-baseline --full 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('scaffold c5 300k-anchors', round(d['value'], 1), round(d['ms_per_step'], 4), d['config']['num_rendered'])" >> $OUT
