@@ -230,6 +230,72 @@ int segs_rasterize_forward_resident_projected(char* geom_buffer, char* binning_b
                                               int geom_rows, int P, const float* background, int width, int height,
                                               float* out_color, uint32_t* status, void* stream);
 
+/* ---- Depth and opacity maps (no reference counterpart: the reference's rasterizer returns colour only).
+ * With the same contributors as the colour (alpha >= 1/255, power <= 0, the 0.99 clamp, the early stop, n_contrib):
+ *   depth[p] = sum_i z_i alpha_i T_i    z_i = the view-space depth the depth sort keys on; no background term (the
+ *                                       un-normalised expected depth: depth / alpha is the normalised one)
+ *   alpha[p] = 1 - T_final[p]           T_final = the transmittance the image scratch keeps for the backward
+ * Pixels no Gaussian reaches get 0 in both.  Maps are (H, W) float32, device memory.  In either struct a NULL field is not
+ * written / is taken as zero, and a NULL struct pointer makes the call exactly the entry point it extends.  The backward twins
+ * take the gradients of the two maps; they run the vector-FMA form of the tile backward even under SEGS_RASTER_MFMA_MOMENTS. */
+typedef struct segs_depth_outputs {
+  float* depth;   /* H x W, or NULL */
+  float* alpha;   /* H x W, or NULL */
+} segs_depth_outputs;
+typedef struct segs_depth_grads {
+  const float* dL_ddepth;   /* H x W, or NULL (zero) */
+  const float* dL_dalpha;   /* H x W, or NULL (zero) */
+} segs_depth_grads;
+/* extends segs_rasterize_forward (+ depth_out) */
+int segs_rasterize_forward_depth(segs_alloc_fn geometry_alloc, void* geometry_ctx,
+                                 segs_alloc_fn binning_alloc, void* binning_ctx,
+                                 segs_alloc_fn image_alloc, void* image_ctx,
+                                 int P, int D, int M,
+                                 const float* background, int width, int height,
+                                 const float* means3D, const float* shs, const float* colors_precomp,
+                                 const float* opacities, const float* scales, float scale_modifier,
+                                 const float* rotations, const float* cov3D_precomp,
+                                 const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                 float tan_fovx, float tan_fovy, int prefiltered,
+                                 float* out_color, int* radii, const segs_depth_outputs* depth_out, void* stream,
+                                 int* num_rendered);
+/* extends segs_rasterize_backward (+ depth_grads) */
+int segs_rasterize_backward_depth(int P, int D, int M, int R,
+                                  const float* background, int width, int height,
+                                  const float* means3D, const float* shs, const float* colors_precomp,
+                                  const float* scales, float scale_modifier, const float* rotations,
+                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                  const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                  char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                  const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                  float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                  float* dL_dscale, float* dL_drot, const segs_depth_grads* depth_grads, void* stream);
+/* extends segs_rasterize_forward_resident (+ depth_out) */
+int segs_rasterize_forward_resident_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,
+                                          int geom_rows, int P, int D, int M, const float* background, int width, int height,
+                                          const float* means3D, const float* shs, const float* colors_precomp,
+                                          const float* opacities, const float* scales, float scale_modifier,
+                                          const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                          const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                                          float* out_color, int* radii, uint32_t* status, const segs_depth_outputs* depth_out,
+                                          void* stream);
+/* extends segs_rasterize_forward_resident_projected (+ depth_out) */
+int segs_rasterize_forward_resident_projected_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,
+                                                    int geom_rows, int P, const float* background, int width, int height,
+                                                    float* out_color, uint32_t* status, const segs_depth_outputs* depth_out,
+                                                    void* stream);
+/* extends segs_rasterize_backward_resident (+ depth_grads); like it, it keeps the accumulator rows clean, the depth row slot
+ * included, so a plain resident backward after a depth one starts from zero */
+int segs_rasterize_backward_resident_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,
+                                           int geom_rows, int P, int D, int M, const float* background, int width, int height,
+                                           const float* means3D, const float* shs, const float* scales, float scale_modifier,
+                                           const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                           const int* radii, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                                           float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                                           float* dL_dsh, float* dL_dscale, float* dL_drot, const segs_depth_grads* depth_grads,
+                                           void* stream);
+
 /* ---- Measurement support (bench.py): per-kernel timing with HIP events recorded on the launch stream.
  * kernel_mask bit i selects kernel id i (ids 0..segs_profile_kernel_count()-1, names via
  * segs_profile_kernel_name).  segs_profile_end() synchronises the recorded events and accumulates;

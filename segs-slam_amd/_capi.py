@@ -30,6 +30,16 @@ class ProjectionTargets(C.Structure):
                 ("tile_ranges", C.c_void_p), ("depth_overflow", C.c_void_p), ("num_tiles", C.c_int), ("flags", C.c_uint32)]
 
 
+class DepthOutputs(C.Structure):
+    """segs_depth_outputs (include/segs_raster.h)."""
+    _fields_ = [("depth", C.c_void_p), ("alpha", C.c_void_p)]
+
+
+class DepthGrads(C.Structure):
+    """segs_depth_grads (include/segs_raster.h)."""
+    _fields_ = [("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p)]
+
+
 class AdamSegment(C.Structure):
     """segs_adam_segment (include/segs_train.h)."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_double)]
@@ -64,6 +74,14 @@ SYMBOLS = {
     "segs_rasterize_forward_resident_projected": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "segs_rasterize_backward_resident": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp,
                                                _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+# the `_depth` twins: the entry point they extend plus one struct pointer in front of `stream`
+for _name in ("segs_rasterize_forward", "segs_rasterize_backward", "segs_rasterize_forward_resident",
+              "segs_rasterize_forward_resident_projected", "segs_rasterize_backward_resident"):
+    _res, _args = SYMBOLS[_name]
+    _at = len(_args) - (2 if _name == "segs_rasterize_forward" else 1)   # (segs_rasterize_forward ends with stream, num_rendered)
+    SYMBOLS[_name + "_depth"] = (_res, _args[:_at] + [_vp] + _args[_at:])
+SYMBOLS.update({
     "segs_visible_filter": (_i, [_i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp]),
     "segs_visible_filter_log_scales": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _vp, _vp]),
     "segs_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
@@ -105,7 +123,7 @@ SYMBOLS = {
     "segs_profile_kernel_count": (_i, []),
     "segs_profile_kernel_name": (C.c_char_p, [_i]),
     "segs_profile_query": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
-}
+})
 
 _lib = None
 

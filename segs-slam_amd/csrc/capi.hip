@@ -313,6 +313,20 @@ int run_binning(const Geom& G, char* bin, const BinningLayout& BL, const GaussSo
   return SEGS_OK;
 }
 
+// K10: the plain tile forward, or its depth form when the caller asked for a depth or an alpha map (segs_*_depth entry points).
+int launch_render_fwd(uint32_t tiles, const uint2* ranges, const uint32_t* point_list, int width, int height, const float* rec,
+                      const float* background, float* final_T, uint32_t* n_contrib, float* out_color, const segs_depth_outputs* dout,
+                      hipStream_t st) {
+  PROF(K_RENDER_FWD);
+  if (dout && (dout->depth || dout->alpha))
+    render_fwd_depth_kernel<<<tiles, 256, 0, st>>>(ranges, point_list, width, height, rec, background, final_T, n_contrib, out_color,
+                                                   dout->depth, dout->alpha);
+  else
+    render_fwd_kernel<<<tiles, 256, 0, st>>>(ranges, point_list, width, height, rec, background, final_T, n_contrib, out_color);
+  LAUNCH_TRY("render_fwd_kernel");
+  return SEGS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -335,13 +349,13 @@ size_t segs_geometry_bytes(int P) { return geom_layout(P < 0 ? 0 : P).total; }
 size_t segs_image_bytes(int width, int height) { return image_layout(width, height).total; }
 size_t segs_binning_bytes(int num_rendered) { return binning_layout(num_rendered < 0 ? 0 : num_rendered).total; }
 
-int segs_rasterize_forward(segs_alloc_fn geometry_alloc, void* geometry_ctx, segs_alloc_fn binning_alloc, void* binning_ctx,
+static int rasterize_forward_impl(segs_alloc_fn geometry_alloc, void* geometry_ctx, segs_alloc_fn binning_alloc, void* binning_ctx,
                            segs_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
                            int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
                            const float* opacities, const float* scales, float scale_modifier, const float* rotations,
                            const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                            const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
-                           int* radii, void* stream, int* num_rendered) {
+                           int* radii, const segs_depth_outputs* dout, void* stream, int* num_rendered) {
   (void)prefiltered;
   hipStream_t st = (hipStream_t)stream;
   if (!geometry_alloc || !binning_alloc || !image_alloc) return fail(SEGS_ERR_INVALID_ARGUMENT, "null allocator callback");
@@ -419,13 +433,37 @@ int segs_rasterize_forward(segs_alloc_fn geometry_alloc, void* geometry_ctx, seg
                        : run_binning(G, bin, BL, GS, ranges, P, R, nullptr, dmin, dbits, dmin + dspan, gx, gy, total_scratch, st, false, tight, nine);
     if (rc) return rc;
   }
-  { PROF(K_RENDER_FWD);
-  render_fwd_kernel<<<gx * gy, 256, 0, st>>>(ranges, (const uint32_t*)(bin + BL.vals[0]), width, height, G.rec(),
-                                                  background, (float*)(img + IL.final_T), (uint32_t*)(img + IL.n_contrib), out_color);
-  }
-  LAUNCH_TRY("render_fwd_kernel");
+  const int rc = launch_render_fwd(gx * gy, ranges, (const uint32_t*)(bin + BL.vals[0]), width, height, G.rec(), background,
+                                   (float*)(img + IL.final_T), (uint32_t*)(img + IL.n_contrib), out_color, dout, st);
+  if (rc) return rc;
   *num_rendered = R;
   return SEGS_OK;
+}
+
+int segs_rasterize_forward(segs_alloc_fn geometry_alloc, void* geometry_ctx, segs_alloc_fn binning_alloc, void* binning_ctx,
+                           segs_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
+                           int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                           const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                           const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                           int* radii, void* stream, int* num_rendered) {
+  return rasterize_forward_impl(geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background,
+                                width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, radii, nullptr, stream,
+                                num_rendered);
+}
+
+int segs_rasterize_forward_depth(segs_alloc_fn geometry_alloc, void* geometry_ctx, segs_alloc_fn binning_alloc, void* binning_ctx,
+                                 segs_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
+                                 int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                                 const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                                 const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                 const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                                 int* radii, const segs_depth_outputs* depth_out, void* stream, int* num_rendered) {
+  return rasterize_forward_impl(geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background,
+                                width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, radii, depth_out, stream,
+                                num_rendered);
 }
 
 // self_clean (resident entry point): the per-Gaussian accumulator rows are not cleared by a memset before the tile kernel;
@@ -438,7 +476,7 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
                             float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                             const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                            bool self_clean, int geom_rows) {
+                            bool self_clean, int geom_rows, const segs_depth_grads* dgrad) {
   hipStream_t st = (hipStream_t)stream;
   if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(SEGS_ERR_INVALID_ARGUMENT, "bad sizes");
   if (geom_rows < P) return fail(SEGS_ERR_INVALID_ARGUMENT, "geom_rows must be >= P");
@@ -463,7 +501,20 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
   if (!self_clean) { PROF(K_MEMSET);
   HIP_TRY(hipMemsetAsync(G.gacc(), 0, (size_t)P * GACC_DWORDS * 4, st));
   }
-  if (R > 0) {
+  // depth form: the gradients of the depth / alpha maps of segs_rasterize_forward*_depth.  It is the VALU form of the tile backward
+  // only: SEGS_RASTER_MFMA_MOMENTS (an A/B switch of the plain kernel) does not apply to it.
+  const float* dL_ddepth = dgrad ? dgrad->dL_ddepth : nullptr;
+  const float* dL_dalpha = dgrad ? dgrad->dL_dalpha : nullptr;
+  const bool depth_form = dL_ddepth || dL_dalpha;
+  if (R > 0 && depth_form) {
+    { PROF(K_RENDER_BWD);
+    render_bwd_depth_kernel<<<(gx * gy + 7) / 8 * 32, 64, 0, st>>>((const uint2*)(img + IL.ranges), (const uint32_t*)(bin + BL.vals[0]), width,
+                                                                  height, G.rec(), background, (const float*)(img + IL.final_T),
+                                                                  (const uint32_t*)(img + IL.n_contrib), dL_dpix, G.gacc(), gx * gy,
+                                                                  dL_ddepth, dL_dalpha);
+    }
+    LAUNCH_TRY("render_bwd_depth_kernel");
+  } else if (R > 0) {
     { PROF(K_RENDER_BWD);
     static const bool mfma_env = [] { const char* e = getenv("SEGS_RENDER_BWD_MFMA"); return e && e[0] == '1'; }();   // measurement A/B only
     ((mfma_env || (g_flags & SEGS_RASTER_MFMA_MOMENTS)) ? render_bwd_mfma_kernel : render_bwd_kernel)<<<(gx * gy + 7) / 8 * 32, 64, 0, st>>>((const uint2*)(img + IL.ranges), (const uint32_t*)(bin + BL.vals[0]), width,
@@ -473,7 +524,8 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
     LAUNCH_TRY("render_bwd_kernel");
   }
   { PROF(K_PREPROCESS_BWD);
-  preprocess_bwd_kernel<<<G.L.nblocks, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
+  // row dword [9] (dL/dz) is only ever non-zero after a depth-map gradient; every clear of a row covers it either way
+  (dL_ddepth ? preprocess_bwd_kernel<true> : preprocess_bwd_kernel<false>)<<<G.L.nblocks, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
                                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x, focal_y,
                                                      tan_fovx, tan_fovy, G.gacc(), (float)width, (float)height, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
                                                      dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, self_clean ? 1 : 0);
@@ -497,7 +549,22 @@ int segs_rasterize_backward(int P, int D, int M, int R, const float* background,
   return rasterize_backward_impl(P, D, M, R, background, width, height, means3D, shs, scales, scale_modifier, rotations,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
                                  image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                 dL_dscale, dL_drot, stream, false, P);
+                                 dL_dscale, dL_drot, stream, false, P, nullptr);
+}
+
+int segs_rasterize_backward_depth(int P, int D, int M, int R, const float* background, int width, int height,
+                                  const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                                  float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                  float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                  const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                  float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                  const segs_depth_grads* depth_grads, void* stream) {
+  (void)colors_precomp;
+  return rasterize_backward_impl(P, D, M, R, background, width, height, means3D, shs, scales, scale_modifier, rotations,
+                                 cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+                                 image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                 dL_dscale, dL_drot, stream, false, P, depth_grads);
 }
 
 static int visible_filter_impl(int P, int width, int height, const float* means3D, const float* scales, int log_scale_stride,
@@ -620,7 +687,7 @@ int segs_debug_preprocess_backward(int P, int width, int height, const float* me
   if (!means3D || !radii || !viewmatrix || !projmatrix || !dL_dmean2D || !dL_dconic || !dL_dmean3D || !dL_dcov3D)
     return fail(SEGS_ERR_INVALID_ARGUMENT, "null pointer");
   const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
-  preprocess_bwd_kernel<<<(P + 255) / 256, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
+  preprocess_bwd_kernel<false><<<(P + 255) / 256, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
                                                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x, focal_y,
                                                          tan_fovx, tan_fovy, nullptr, (float)width, (float)height, const_cast<float*>(dL_dmean2D),
                                                          const_cast<float*>(dL_dconic), nullptr, nullptr, dL_dmean3D, dL_dcov3D,
@@ -685,12 +752,12 @@ int segs_project2_image(int P, int D, int M, int width, int height, const float*
 // ---- Resident (steady-state) variants: no host synchronisation, fixed launch sequence (hipGraph-capturable). ----
 size_t segs_resident_binning_bytes(int P, int capacity) { return gauss_sort_layout(capacity < 0 ? 0 : capacity, P < 0 ? 0 : P).total; }
 
-int segs_rasterize_forward_resident(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P, int D, int M,
+static int rasterize_forward_resident_impl(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P, int D, int M,
                                     const float* background, int width, int height, const float* means3D, const float* shs,
                                     const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
                                     const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                                     const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, float* out_color,
-                                    int* radii, uint32_t* status, void* stream) {
+                                    int* radii, uint32_t* status, const segs_depth_outputs* dout, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (P <= 0 || capacity <= 0 || width <= 0 || height <= 0) return fail(SEGS_ERR_INVALID_ARGUMENT, "bad sizes");
   if (geom_rows < P) return fail(SEGS_ERR_INVALID_ARGUMENT, "geom_rows (rows the geometry buffer was sized for) must be >= P");
@@ -728,12 +795,31 @@ int segs_rasterize_forward_resident(char* geom_buffer, char* binning_buffer, cha
                    (g_flags & SEGS_RASTER_KEEP_DEAD_INSTANCES) == 0u, true);
   if (rc) return rc;
   // status[3] (overflow) and the host mirror are written by identify_tile_ranges_kernel at the end of run_binning
-  { PROF(K_RENDER_FWD);
-  render_fwd_kernel<<<gx * gy, 256, 0, st>>>(ranges, (const uint32_t*)(bin + BL.vals[0]), width, height, G.rec(), background,
-                                                  (float*)(img + IL.final_T), (uint32_t*)(img + IL.n_contrib), out_color);
-  }
-  LAUNCH_TRY("render_fwd_kernel");
-  return SEGS_OK;
+  return launch_render_fwd(gx * gy, ranges, (const uint32_t*)(bin + BL.vals[0]), width, height, G.rec(), background,
+                           (float*)(img + IL.final_T), (uint32_t*)(img + IL.n_contrib), out_color, dout, st);
+}
+
+int segs_rasterize_forward_resident(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P, int D, int M,
+                                    const float* background, int width, int height, const float* means3D, const float* shs,
+                                    const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                                    const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                    const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, float* out_color,
+                                    int* radii, uint32_t* status, void* stream) {
+  return rasterize_forward_resident_impl(geom_buffer, binning_buffer, image_buffer, capacity, geom_rows, P, D, M, background, width, height,
+                                         means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                         viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, radii, status, nullptr, stream);
+}
+
+int segs_rasterize_forward_resident_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P,
+                                          int D, int M, const float* background, int width, int height, const float* means3D,
+                                          const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                                          float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                          const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                                          float tan_fovy, float* out_color, int* radii, uint32_t* status,
+                                          const segs_depth_outputs* depth_out, void* stream) {
+  return rasterize_forward_resident_impl(geom_buffer, binning_buffer, image_buffer, capacity, geom_rows, P, D, M, background, width, height,
+                                         means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                         viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, radii, status, depth_out, stream);
 }
 
 // ---- K1 done by the producer of the Gaussians (segs_neural_forward_projected): where its outputs go, and the forward without K1.
@@ -760,9 +846,9 @@ int segs_resident_projection_targets(char* geom_buffer, char* binning_buffer, ch
   return SEGS_OK;
 }
 
-int segs_rasterize_forward_resident_projected(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P,
-                                              const float* background, int width, int height, float* out_color, uint32_t* status,
-                                              void* stream) {
+static int rasterize_forward_resident_projected_impl(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,
+                                                    int geom_rows, int P, const float* background, int width, int height, float* out_color,
+                                                    uint32_t* status, const segs_depth_outputs* dout, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (P <= 0 || capacity <= 0 || width <= 0 || height <= 0) return fail(SEGS_ERR_INVALID_ARGUMENT, "bad sizes");
   if (geom_rows < P) return fail(SEGS_ERR_INVALID_ARGUMENT, "geom_rows (rows the geometry buffer was sized for) must be >= P");
@@ -781,12 +867,23 @@ int segs_rasterize_forward_resident_projected(char* geom_buffer, char* binning_b
   int rc = run_binning(G, bin, BL, GS, ranges, P, capacity, status, DEPTH_KEY_MIN, DEPTH_KEY_BITS, 0xFFFFFFFFu, gx, gy, status, st, true,
                        (g_flags & SEGS_RASTER_KEEP_DEAD_INSTANCES) == 0u, true);
   if (rc) return rc;
-  { PROF(K_RENDER_FWD);
-  render_fwd_kernel<<<gx * gy, 256, 0, st>>>(ranges, (const uint32_t*)(bin + BL.vals[0]), width, height, G.rec(), background,
-                                                  (float*)(img + IL.final_T), (uint32_t*)(img + IL.n_contrib), out_color);
-  }
-  LAUNCH_TRY("render_fwd_kernel");
-  return SEGS_OK;
+  return launch_render_fwd(gx * gy, ranges, (const uint32_t*)(bin + BL.vals[0]), width, height, G.rec(), background,
+                           (float*)(img + IL.final_T), (uint32_t*)(img + IL.n_contrib), out_color, dout, st);
+}
+
+int segs_rasterize_forward_resident_projected(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P,
+                                              const float* background, int width, int height, float* out_color, uint32_t* status,
+                                              void* stream) {
+  return rasterize_forward_resident_projected_impl(geom_buffer, binning_buffer, image_buffer, capacity, geom_rows, P, background, width,
+                                                   height, out_color, status, nullptr, stream);
+}
+
+int segs_rasterize_forward_resident_projected_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,
+                                                    int geom_rows, int P, const float* background, int width, int height,
+                                                    float* out_color, uint32_t* status, const segs_depth_outputs* depth_out,
+                                                    void* stream) {
+  return rasterize_forward_resident_projected_impl(geom_buffer, binning_buffer, image_buffer, capacity, geom_rows, P, background, width,
+                                                   height, out_color, status, depth_out, stream);
 }
 
 int segs_rasterize_backward_resident(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P, int D, int M,
@@ -801,7 +898,21 @@ int segs_rasterize_backward_resident(char* geom_buffer, char* binning_buffer, ch
   return rasterize_backward_impl(P, D, M, capacity, background, width, height, means3D, shs, scales, scale_modifier, rotations,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
                                  image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                 dL_dscale, dL_drot, stream, true, geom_rows);
+                                 dL_dscale, dL_drot, stream, true, geom_rows, nullptr);
+}
+
+int segs_rasterize_backward_resident_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P,
+                                           int D, int M, const float* background, int width, int height, const float* means3D,
+                                           const float* shs, const float* scales, float scale_modifier, const float* rotations,
+                                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                           const float* campos, float tan_fovx, float tan_fovy, const int* radii, const float* dL_dpix,
+                                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                                           float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                           const segs_depth_grads* depth_grads, void* stream) {
+  return rasterize_backward_impl(P, D, M, capacity, background, width, height, means3D, shs, scales, scale_modifier, rotations,
+                                 cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+                                 image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                 dL_dscale, dL_drot, stream, true, geom_rows, depth_grads);
 }
 
 // ---- measurement support (bench.py): HIP events recorded on the launch stream around selected kernels.

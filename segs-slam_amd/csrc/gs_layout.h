@@ -47,7 +47,8 @@ constexpr uint32_t ID_MASK = (1u << ID_BITS) - 1u;
 constexpr int MAX_GAUSSIANS = 1 << ID_BITS;
 
 // Gradient accumulation row, 16 dwords (64 B), raw moments of the tile backward (render.hip): [0,1] Mx My  [2,3,4] Mxx Mxy Myy
-// [5] dL/dopacity (= S0 / opacity)  [6,7,8] dL/dcolor.
+// [5] dL/dopacity (= S0 / opacity)  [6,7,8] dL/dcolor  [9] dL/dz of the view depth (depth backward only; 0 otherwise).
+// Every row clear, by the memset of the synchronising backward or the write-back of preprocess_bwd_kernel, covers [0..11].
 constexpr int GACC_DWORDS = 16;
 
 constexpr size_t ALIGN = 256;

@@ -36,6 +36,7 @@ __global__ void visible_filter_kernel(
 __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __restrict__ viewmatrix,
                                     uint8_t* __restrict__ present);
 
+template <bool DEPTH>   // DEPTH: + row dword [9] (dL/dz of the depth map, render_bwd_depth_kernel) into dL/dmean3D
 __global__ void preprocess_bwd_kernel(
     int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,
     const float* __restrict__ rotations, float mod, const float* __restrict__ cov3D_precomp,
@@ -98,6 +99,17 @@ __global__ void render_bwd_mfma_kernel(const uint2* __restrict__ ranges, const u
                                        const float* __restrict__ rec, const float* __restrict__ bg,
                                        const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
                                        const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles);
+// Depth forms (no reference counterpart): render_fwd_kernel + out_depth = sum z alpha T and out_alpha = 1 - final_T (either may be
+// null); render_bwd_kernel + the gradients of those maps (either may be null), dL/dz into row dword [9].
+__global__ void render_fwd_depth_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
+                                        const float* __restrict__ rec, const float* __restrict__ bg,
+                                        float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
+                                        float* __restrict__ out_depth, float* __restrict__ out_alpha);
+__global__ void render_bwd_depth_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
+                                        const float* __restrict__ rec, const float* __restrict__ bg,
+                                        const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                                        const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+                                        const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha);
 
 // ---- debug / test support (binning.hip)
 __global__ void unpack_geometry_kernel(int P, const float* __restrict__ rec, const BinInfo* __restrict__ bin,

@@ -5,6 +5,7 @@
 //   mark_visible_kernel     K4  reference: checkFrustum            cuda_rasterizer/rasterizer_impl.cu:54-66
 //   preprocess_bwd_kernel   K12+K13 fused; reference: computeCov2DCUDA backward.cu:144-274,
 //                           preprocessCUDA backward.cu:346-396, computeCov3D backward.cu:278-341
+//                           <true>: + the depth map's dL/dz (row dword [9]); no reference counterpart
 //
 // All are HBM-bound streaming kernels (one Gaussian per lane, 256-thread workgroups):
 //  * the (P,3) AoS inputs are fetched as three fully coalesced dword sweeps per workgroup and
@@ -268,6 +269,10 @@ __device__ __forceinline__ void quat_rows(float4 q, float R[3][3]) {   // standa
 
 // gacc rows hold the tile kernel's per-Gaussian sums (gs_layout.h); if gacc is null the caller supplied dL_dmean2D /
 // dL_dconic directly (segs_debug_preprocess_backward: this stage alone against the oracle).
+// DEPTH (after render_bwd_depth_kernel): row dword [9] holds dL/dz of the view-space depth z = V[2] x + V[6] y + V[10] z + V[14]
+// that the depth map composites, which adds dL/dz (V[2], V[6], V[10]) to dL/dmean3D.  A template KERNEL, not a kernel wrapping
+// an inlined body: the wrapped form of <false> came out with 92 instead of 86 VGPRs.
+template <bool DEPTH>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
     int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,
     const float* __restrict__ rotations, float mod, const float* __restrict__ cov3D_precomp,
@@ -287,7 +292,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
   // ---- what arrives from the tile kernel
   float g2x = 0.f, g2y = 0.f;            // dL/dmean2D, NDC-scaled (backward.cu:541-542)
   Sym2 G{0.f, 0.f, 0.f};                 // dL/dconic
-  float dcol0 = 0.f, dcol1 = 0.f, dcol2 = 0.f, dop = 0.f;
+  float dcol0 = 0.f, dcol1 = 0.f, dcol2 = 0.f, dop = 0.f, dz = 0.f;
   float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;   // the tile kernel's row: Mx My Mxx Mxy | Myy dL/dopacity Sr Sg | Sb
   if (gacc) {
     // Rows hold raw moments (render.hip): sums over the (pixel, Gaussian) pairs of w = dL/dG * G times 1, dx, dy, dx^2, ...;
@@ -322,6 +327,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
         if ((lane >> 5) == half) {
           const float4* mine = reinterpret_cast<const float4*>(wl + (lane & 31) * GACC_DWORDS);
           a0 = mine[0]; a1 = mine[1]; dcol2 = wl[(lane & 31) * GACC_DWORDS + 8];
+          if (DEPTH) dz = wl[(lane & 31) * GACC_DWORDS + 9];
         }
         asm volatile("" ::: "memory");
       }
@@ -444,6 +450,10 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
       const float from_proj = (proj[4 * j] * w - proj[4 * j + 3] * ux) * g2x + (proj[4 * j + 1] * w - proj[4 * j + 3] * uy) * g2y;
       out_mean[j] = from_cov + from_proj;
     }
+    if (DEPTH) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) out_mean[j] += dz * view[4 * j + 2];
+    }
     // ---- scales and rotation: dL/dL = 2 M2^T (Dc U)
     if (scales) {
       float DU[2][3];
@@ -478,6 +488,12 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
   }
   if (dL_drot) reinterpret_cast<float4*>(dL_drot)[idx] = make_float4(out_rot[0], out_rot[1], out_rot[2], out_rot[3]);
 }
+
+#define SEGS_PREPROCESS_BWD_ARGS int, const float*, const int*, const float*, const float*, float, const float*, const float*, \
+    const float*, float, float, float, float, float*, float, float, float*, float*, float*, float*, float*, float*, float*, float*, int
+template __global__ void preprocess_bwd_kernel<false>(SEGS_PREPROCESS_BWD_ARGS);
+template __global__ void preprocess_bwd_kernel<true>(SEGS_PREPROCESS_BWD_ARGS);
+#undef SEGS_PREPROCESS_BWD_ARGS
 
 // SH colour branch only (callers that pass `shs`; off the live SEGS-SLAM path): dL/dsh and the view-direction term of
 // dL/dmean3D from the summed dL/dcolor (backward.cu:390-391), as a pass of its own so that its tables stay out of the

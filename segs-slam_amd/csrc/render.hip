@@ -2,6 +2,8 @@
 //
 //   render_fwd_kernel  K10  reference: renderCUDA forward   cuda_rasterizer/forward.cu:339-452
 //   render_bwd_kernel  K11  reference: renderCUDA backward  cuda_rasterizer/backward.cu:399-557
+//   render_fwd_depth_kernel / render_bwd_depth_kernel: the same two plus a depth map (sum z alpha T) and an alpha map
+//                      (1 - final_T) and their gradients -- template instantiations of the same bodies; no reference counterpart
 //
 // Neither kernel is HBM-bound: per (Gaussian, 8x8 quadrant) the forward issues ~22 vector instructions, the backward ~39,
 // against 64 B of record; the forward is VALU-issue bound, the backward VALU- and LDS-bound at once.
@@ -77,12 +79,23 @@ __device__ __forceinline__ Compacted compact_chunk(uint32_t v, uint32_t qbit, in
   return c;
 }
 
-constexpr int FWD_REC = 12;  // floats per staged record: x y a2 b2 | c2 o r g | b pos - -
+constexpr int FWD_REC = 12;  // floats per staged record: x y a2 b2 | c2 o r g | b pos z -   (z: DEPTH only)
 
-__global__ void __launch_bounds__(256) render_fwd_kernel(
+// A 64-byte record's dwords [8] (b), or [8..9] (b, view-space z) as one 8-byte load for the depth form.
+template <bool DEPTH>
+__device__ __forceinline__ void load_rec_tail(const float4* p, float& rb, float& rz) {
+  if (DEPTH) { const float2 t = reinterpret_cast<const float2*>(p)[4]; rb = t.x; rz = t.y; }
+  else rb = reinterpret_cast<const float*>(p)[8];
+}
+
+// DEPTH = true also composites the view-space z of the same contributors into out_depth = sum z alpha T (no background
+// term) and writes out_alpha = 1 - final_T; either pointer may be null.  DEPTH = false is render_fwd_kernel as it was.
+template <bool DEPTH>
+__device__ __forceinline__ void render_fwd_body(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, float* __restrict__ final_T,
-    uint32_t* __restrict__ n_contrib, float* __restrict__ out_color) {
+    uint32_t* __restrict__ n_contrib, float* __restrict__ out_color, float* __restrict__ out_depth,
+    float* __restrict__ out_alpha) {
   __shared__ float4 s_rec[4][64][FWD_REC / 4];
   const uint32_t tiles_x = (W + TILE_X - 1) / TILE_X;
   const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
@@ -99,14 +112,14 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
   // Per-pixel state.  A pixel that has terminated ("dead") keeps T = 0 and thr = -1, which makes every later
   // Gaussian a no-op for it without any per-lane branch: w = alpha*T = 0 and the stop test T' < thr is false.
   float T = inside ? 1.0f : 0.f, thr = inside ? 0.0001f : -1.f;
-  float Tfin = 0.f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+  float Tfin = 0.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dz = 0.f;
   uint32_t last = 0u, lastfin = 0u;
 
   // Software pipeline over 64-entry chunks of the tile list: while chunk c is evaluated, the records of chunk
   // c+1 (gathered one per lane, compacted order) and the list entries of chunk c+2 are in flight.
   uint32_t v_nxt, v_nn = 0u;
   Compacted cc;
-  float4 r0, r1; float rb;
+  float4 r0, r1; float rb, rz = 0.f;
   {
     const uint32_t i0 = range.x + lane, i1 = range.x + 64 + lane;
     const uint32_t v0 = i0 < range.y ? point_list[i0] : 0u;
@@ -115,7 +128,7 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
     r0 = make_float4(0.f, 0.f, 0.f, 0.f); r1 = r0; rb = 0.f;
     if (lane < cc.n) {
       const float4* p = reinterpret_cast<const float4*>(rec + (size_t)(cc.val & ID_MASK) * REC_DWORDS);
-      r0 = p[0]; r1 = p[1]; rb = reinterpret_cast<const float*>(p)[8];
+      r0 = p[0]; r1 = p[1]; load_rec_tail<DEPTH>(p, rb, rz);
     }
   }
   bool alive = true;  // wave-uniform: some pixel of this 8x8 block still accumulates
@@ -129,7 +142,7 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
       const bool real = lane < n;
       s_rec[wv][lane][0] = real ? r0 : make_float4(0.f, 0.f, 0.f, 0.f);
       s_rec[wv][lane][1] = real ? r1 : make_float4(0.f, 0.f, 0.f, 0.f);
-      s_rec[wv][lane][2] = make_float4(real ? rb : 0.f, __uint_as_float(base - range.x + cc.pos + 1u), 0.f, 0.f);
+      s_rec[wv][lane][2] = make_float4(real ? rb : 0.f, __uint_as_float(base - range.x + cc.pos + 1u), (DEPTH && real) ? rz : 0.f, 0.f);
     }
     wave_lds_fence();
     // put chunk c+1's records and chunk c+2's list entries in flight
@@ -139,7 +152,7 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
       cc = compact_chunk<false>(v_nxt, qbit, lane);
       if (lane < cc.n) {
         const float4* p = reinterpret_cast<const float4*>(rec + (size_t)(cc.val & ID_MASK) * REC_DWORDS);
-        r0 = p[0]; r1 = p[1]; rb = reinterpret_cast<const float*>(p)[8];
+        r0 = p[0]; r1 = p[1]; load_rec_tail<DEPTH>(p, rb, rz);
       }
       v_nxt = v_nn;
     }
@@ -149,6 +162,7 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
       const int k = k0 + u;
       const float4 q0 = s_rec[wv][k][0], q1 = s_rec[wv][k][1];
       const float2 q2 = *reinterpret_cast<const float2*>(&s_rec[wv][k][2]);
+      const float qz = DEPTH ? s_rec[wv][k][2].z : 0.f;
       const float dx = q0.x - pxf, dy = q0.y - pyf;
       const float power2 = dx * (q0.z * dx + q0.w * dy) + (q1.x * dy) * dy;  // log2e * power
       const float alpha = fminf(0.99f, q1.y * fast_exp2(power2));
@@ -167,6 +181,7 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
       }
       T = test_T;
       C0 += q1.z * w; C1 += q1.w * w; C2 += q2.x * w;
+      if (DEPTH) Dz += qz * w;
       last = ok ? __float_as_uint(q2.y) : last;
       if (!alive) break;
     }
@@ -182,7 +197,25 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(
     out_color[pix_id] = C0 + Tout * bg[0];
     out_color[HW + pix_id] = C1 + Tout * bg[1];
     out_color[2 * HW + pix_id] = C2 + Tout * bg[2];
+    if (DEPTH) {
+      if (out_depth) out_depth[pix_id] = Dz;
+      if (out_alpha) out_alpha[pix_id] = 1.0f - Tout;
+    }
   }
+}
+
+__global__ void __launch_bounds__(256) render_fwd_kernel(
+    const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
+    const float* __restrict__ rec, const float* __restrict__ bg, float* __restrict__ final_T,
+    uint32_t* __restrict__ n_contrib, float* __restrict__ out_color) {
+  render_fwd_body<false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, out_color, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) render_fwd_depth_kernel(
+    const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
+    const float* __restrict__ rec, const float* __restrict__ bg, float* __restrict__ final_T,
+    uint32_t* __restrict__ n_contrib, float* __restrict__ out_color, float* __restrict__ out_depth,
+    float* __restrict__ out_alpha) {
+  render_fwd_body<true>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, out_color, out_depth, out_alpha);
 }
 
 // ---- cross-lane helpers -----------------------------------------------------------------------
@@ -233,10 +266,13 @@ struct BwdLds {                  // 9088 B per wave -> 16 single-wave workgroups
 
 // Pixel role of the backward kernel over one batch of `nb` staged records (see render_bwd_kernel).  USE_BG = false
 // drops the background term of dL/dalpha (bg . dL/dpixel == 0 for every pixel of the wave: SLAM renders on black).
-template <bool USE_BG>
+// DEPTH: the depth map D = sum z alpha T is a fourth channel of "colour" z with dL/dD = dpz and no background, so z dpz joins
+// the per-pixel dot product and accd tracks the depth behind as well; the alpha map's gradient arrives folded into
+// bg_dot_dpixel by the caller (dA/dalpha_i = T_final / (1 - alpha_i): the background term with the opposite sign).
+template <bool USE_BG, bool DEPTH>
 __device__ __forceinline__ void pixel_role(BwdLds& L, int nb, int lane, float pxf, float pyf, uint32_t last_contributor,
-                                           float dp0, float dp1, float dp2, float T_final, float bg_dot_dpixel, float& T,
-                                           float& accd) {
+                                           float dp0, float dp1, float dp2, float dpz, float T_final, float bg_dot_dpixel,
+                                           float& T, float& accd) {
 #ifndef PIX_UNROLL
 #define PIX_UNROLL 4
 #endif
@@ -244,6 +280,7 @@ __device__ __forceinline__ void pixel_role(BwdLds& L, int nb, int lane, float px
   for (int sl = 0; sl < nb; sl++) {
     const float4 q0 = L.rec[sl][0], q1 = L.rec[sl][1];
     const float2 q2 = *reinterpret_cast<const float2*>(&L.rec[sl][2]);
+    const float qz = DEPTH ? L.rec[sl][2].w : 0.f;
     const float dx = q0.x - pxf, dy = q0.y - pyf;
     const float power2 = dx * (q0.z * dx + q0.w * dy) + (q1.x * dy) * dy;
 #if defined(SEGS_MEASURE) && defined(ABLATE_NO_TRANS)
@@ -264,7 +301,7 @@ __device__ __forceinline__ void pixel_role(BwdLds& L, int nb, int lane, float px
     // The colour accumulated behind this Gaussian enters only through its dot product with dL/dpixel, so ONE running
     // scalar accd = sum_ch accum_ch * g_ch replaces the three accumulators of backward.cu:513-516:
     //   sum_ch (c_ch - accum_ch) g_ch = c.g - accd;   accum' = accum + alpha (c - accum)  =>  accd' = accd + alpha (c.g - accd)
-    const float diff = (q1.z * dp0 + q1.w * dp1 + q2.x * dp2) - accd;
+    const float diff = (DEPTH ? (q1.z * dp0 + q1.w * dp1 + q2.x * dp2 + qz * dpz) : (q1.z * dp0 + q1.w * dp1 + q2.x * dp2)) - accd;
     float dL_dalpha = diff * T;
     if (USE_BG) dL_dalpha += (-T_final * rinv) * bg_dot_dpixel;
     accd += ae * diff;
@@ -274,11 +311,15 @@ __device__ __forceinline__ void pixel_role(BwdLds& L, int nb, int lane, float px
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <bool MFMA>
+// DEPTH (VALU form only): also the gradients of the depth and alpha maps (render_fwd_depth_kernel); dL_ddepth / dL_dalpha
+// may be null (zero).  A tenth per-Gaussian sum, Sz = sum alpha T dL/dD = dL/dz, leaves with the other nine into row dword [9].
+template <bool MFMA, bool DEPTH>
 __device__ __forceinline__ void render_bwd_body(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
-    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles) {
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+    const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha) {
+  static_assert(!(MFMA && DEPTH), "the depth form of the tile backward is the VALU form");
   // One wave (one 8x8 quadrant) per workgroup: the four quadrants of a tile share nothing but their inputs, and as one
   // 256-thread workgroup the three shorter ones held their LDS and wave slots until the longest list ended (the longest
   // quadrant of a tile is 1.15-1.17 x the mean, tools/tile_stats.py).  Workgroup b = ((tl * 4 + q) << 3) | xcd: the four
@@ -306,7 +347,10 @@ __device__ __forceinline__ void render_bwd_body(
   const uint32_t last_contributor = inside ? n_contrib[pix_id] : 0u;
   float dp0 = 0.f, dp1 = 0.f, dp2 = 0.f;
   if (inside) { dp0 = dL_dpix[pix_id]; dp1 = dL_dpix[HW + pix_id]; dp2 = dL_dpix[2 * HW + pix_id]; }
-  const float bg_dot_dpixel = bg[0] * dp0 + bg[1] * dp1 + bg[2] * dp2;
+  float dpz = 0.f, dpa = 0.f;   // dL/dD, dL/dA of this pixel (DEPTH)
+  if (DEPTH && inside) { dpz = dL_ddepth ? dL_ddepth[pix_id] : 0.f; dpa = dL_dalpha ? dL_dalpha[pix_id] : 0.f; }
+  // DEPTH: A = 1 - T_final enters dL/dalpha_i as -T_final / (1 - alpha_i) (-dL/dA), the background's term with the other sign
+  const float bg_dot_dpixel = DEPTH ? (bg[0] * dp0 + bg[1] * dp1 + bg[2] * dp2) - dpa : bg[0] * dp0 + bg[1] * dp1 + bg[2] * dp2;
   const bool use_bg = __ballot(bg_dot_dpixel != 0.f) != 0ull;   // wave-uniform
 
   // Start at the deepest contributor of this 8x8 block (backward.cu:487-488).
@@ -356,7 +400,7 @@ __device__ __forceinline__ void render_bwd_body(
   const int32_t cfirst = (int32_t)((wave_last - 1u) & ~63u);
   uint32_t v_nxt = 0u;
   Compacted cc;
-  float4 r0, r1; float rb;
+  float4 r0, r1; float rb, rz = 0.f;
   {
     const uint32_t p0 = (uint32_t)cfirst + lane;
     const uint32_t v0 = p0 < wave_last ? point_list[range.x + p0] : 0u;
@@ -365,7 +409,7 @@ __device__ __forceinline__ void render_bwd_body(
     r0 = make_float4(0.f, 0.f, 0.f, 0.f); r1 = r0; rb = 0.f;
     if (lane < cc.n) {
       const float4* p = reinterpret_cast<const float4*>(rec + (size_t)(cc.val & ID_MASK) * REC_DWORDS);
-      r0 = p[0]; r1 = p[1]; rb = reinterpret_cast<const float*>(p)[8];
+      r0 = p[0]; r1 = p[1]; load_rec_tail<DEPTH>(p, rb, rz);
     }
   }
   // Batches of BW_SLOTS entries are cut from the STREAM of compacted entries, not from each 64-entry chunk: what a chunk
@@ -379,14 +423,14 @@ __device__ __forceinline__ void render_bwd_body(
     const int n = tail ? 0 : __builtin_amdgcn_readfirstlane(cc.n);
     // current chunk's records stay in registers (one per lane, compacted order); the next chunk's go in flight
     const float4 c0 = r0, c1 = r1;
-    const float4 c2 = make_float4(rb, __uint_as_float((uint32_t)cbase + cc.pos), __uint_as_float(cc.val & ID_MASK), 0.f);
+    const float4 c2 = make_float4(rb, __uint_as_float((uint32_t)cbase + cc.pos), __uint_as_float(cc.val & ID_MASK), DEPTH ? rz : 0.f);
     if (cbase >= 64) {
       uint32_t v_nn = 0u;
       if (cbase >= 128) v_nn = point_list[range.x + (uint32_t)(cbase - 128) + lane];
       cc = compact_chunk<true>(v_nxt, qbit, lane);
       if (lane < cc.n) {
         const float4* p = reinterpret_cast<const float4*>(rec + (size_t)(cc.val & ID_MASK) * REC_DWORDS);
-        r0 = p[0]; r1 = p[1]; rb = reinterpret_cast<const float*>(p)[8];
+        r0 = p[0]; r1 = p[1]; load_rec_tail<DEPTH>(p, rb, rz);
       }
       v_nxt = v_nn;
     }
@@ -403,8 +447,8 @@ __device__ __forceinline__ void render_bwd_body(
       fill = 0;
       wave_lds_fence();
       // ---------------- (1) pixel role
-      if (use_bg) pixel_role<true>(L, nb, lane, pxf, pyf, last_contributor, dp0, dp1, dp2, T_final, bg_dot_dpixel, T, accd);
-      else pixel_role<false>(L, nb, lane, pxf, pyf, last_contributor, dp0, dp1, dp2, T_final, bg_dot_dpixel, T, accd);
+      if (use_bg) pixel_role<true, DEPTH>(L, nb, lane, pxf, pyf, last_contributor, dp0, dp1, dp2, dpz, T_final, bg_dot_dpixel, T, accd);
+      else pixel_role<false, DEPTH>(L, nb, lane, pxf, pyf, last_contributor, dp0, dp1, dp2, dpz, T_final, bg_dot_dpixel, T, accd);
       wave_lds_fence();
 #if defined(SEGS_MEASURE) && defined(ABLATE_NO_GAUSS_ROLE)
       continue;   // (the do-while's condition is evaluated)
@@ -447,7 +491,7 @@ __device__ __forceinline__ void render_bwd_body(
 #pragma unroll
       for (int c = 0; c < 8; c++) { px8[c] = (float)c - cx; px8q[c] = px8[c] * px8[c]; }
       const float pyc0 = pyl0 - cy, pyc1 = pyl1 - cy;
-      float S0, S1x, S1y, Sxx, Sxy, Syy, Sr = 0.f, Sg = 0.f, Sb = 0.f;
+      float S0, S1x, S1y, Sxx, Sxy, Syy, Sr = 0.f, Sg = 0.f, Sb = 0.f, Sz = 0.f;
       {
         float R0[2] = {0.f, 0.f}, R1[2] = {0.f, 0.f}, R2[2] = {0.f, 0.f};
         const float2* warow = &L.wa[gs][part * 16];
@@ -457,6 +501,7 @@ __device__ __forceinline__ void render_bwd_body(
           const float w = wa_i.x, a = wa_i.y;                                                 \
           R0[(i) >> 3] += w; R1[(i) >> 3] += w * px8[(i) & 7]; R2[(i) >> 3] += w * px8q[(i) & 7]; \
           fmac_row_bcast<(i)>(Sr, dp0, a); fmac_row_bcast<(i)>(Sg, dp1, a); fmac_row_bcast<(i)>(Sb, dp2, a); \
+          if (DEPTH) fmac_row_bcast<(i)>(Sz, dpz, a);                                         \
         }
         GAUSS_STEP(0) GAUSS_STEP(1) GAUSS_STEP(2) GAUSS_STEP(3) GAUSS_STEP(4) GAUSS_STEP(5) GAUSS_STEP(6) GAUSS_STEP(7)
         GAUSS_STEP(8) GAUSS_STEP(9) GAUSS_STEP(10) GAUSS_STEP(11) GAUSS_STEP(12) GAUSS_STEP(13) GAUSS_STEP(14) GAUSS_STEP(15)
@@ -468,10 +513,17 @@ __device__ __forceinline__ void render_bwd_body(
       }
       const float g1 = fold_rows4(S0, S1y, S1x, Sxx);   // rows: S0, S1x, S1y, Sxx
       const float g2 = fold_rows4(Sxy, Sr, Syy, Sg);    // rows: Sxy, Syy, Sr, Sg
+      if (DEPTH) {
+        const float g3 = fold_rows4(Sb, Sz, Sb, Sz);    // rows: Sb, Sb, Sz, Sz
+        mom[gs][part] = g1;
+        mom[gs][4 + part] = g2;
+        if ((part & 1) == 0) mom[gs][8 + (part >> 1)] = g3;
+      } else {
       const float g3 = fold_rows4(Sb, Sb, Sb, Sb);      // every row: Sb total
       mom[gs][part] = g1;
       mom[gs][4 + part] = g2;
       if (part == 0) mom[gs][8] = g3;
+      }
       }
       wave_lds_fence();
       {
@@ -496,11 +548,12 @@ __device__ __forceinline__ void render_bwd_body(
         }
       }
       wave_lds_fence();
-      // one atomic wave instruction per 4 slots: lane (row, col<9) adds element col of slot 4j + row
+      // one atomic wave instruction per 4 slots: lane (row, col<9) adds element col of slot 4j + row (DEPTH: col<10, [9] = Sz,
+      // left in mom[slot][9] by the fold and not touched by the shift above)
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const int slot = 4 * j + part;
-        if (slot < nb && gs < 9) {
+        if (slot < nb && gs < (DEPTH ? 10 : 9)) {
           const uint32_t id = __float_as_uint(reinterpret_cast<const float*>(&L.rec[slot][2])[2]);
 #if !(defined(SEGS_MEASURE) && defined(ABLATE_NO_ATOMICS))
           atomicAdd(gacc + (size_t)id * GACC_DWORDS + gs, mom[slot][gs]);
@@ -517,14 +570,22 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles) {
-  render_bwd_body<false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles);
+  render_bwd_body<false, false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, nullptr, nullptr);
 }
 // The Gaussian role's sums on the matrix pipe: the measured A/B partner (SEGS_RENDER_BWD_MFMA=1, capi.hip).
 __global__ void __launch_bounds__(64) render_bwd_mfma_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles) {
-  render_bwd_body<true>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles);
+  render_bwd_body<true, false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, nullptr, nullptr);
+}
+// The depth form (VALU Gaussian role): render_bwd_kernel plus the gradients of render_fwd_depth_kernel's depth and alpha maps.
+__global__ void __launch_bounds__(64) render_bwd_depth_kernel(
+    const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
+    const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+    const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha) {
+  render_bwd_body<false, true>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, dL_ddepth, dL_dalpha);
 }
 
 }  // namespace segs

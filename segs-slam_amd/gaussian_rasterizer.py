@@ -2,6 +2,8 @@
 
 GaussianRasterizationSettings, GaussianRasterizerFunction (autograd), rasterizeGaussians and the
 GaussianRasterizer module keep the reference's names, argument order and error behaviour.
+GaussianRasterizerDepthFunction, rasterizeGaussiansWithDepth and GaussianRasterizer.forward_with_depth have no reference
+counterpart: the same render plus a differentiable depth map (sum z alpha T) and alpha map (1 - T_final).
 """
 from __future__ import annotations
 
@@ -62,10 +64,57 @@ class GaussianRasterizerFunction(torch.autograd.Function):
                 g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
 
 
+class GaussianRasterizerDepthFunction(torch.autograd.Function):
+    """GaussianRasterizerFunction plus the depth and alpha maps (rasterize_points.RasterizeGaussiansDepthCUDA)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        rs = raster_settings
+        num_rendered, color, radii, depth, alpha, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansDepthCUDA(
+            rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3Ds_precomp,
+            rs.viewmatrix_, rs.projmatrix_, rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, sh,
+            rs.sh_degree_, rs.campos_, rs.prefiltered_)
+        ctx.num_rendered = num_rendered
+        ctx.scale_modifier = rs.scale_modifier_
+        ctx.tanfovx, ctx.tanfovy = rs.tanfovx_, rs.tanfovy_
+        ctx.sh_degree = rs.sh_degree_
+        ctx.save_for_backward(rs.bg_, rs.viewmatrix_, rs.projmatrix_, rs.campos_, colors_precomp, means3D, scales,
+                              rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)   # an unused map's gradient stays None and is passed down as NULL (no work for it)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii=None, grad_depth=None, grad_alpha=None):
+        (bg, viewmatrix, projmatrix, campos, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
+         geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 9
+        if grad_out_color is None:
+            ref = grad_depth if grad_depth is not None else grad_alpha
+            grad_out_color = torch.zeros((3,) + tuple(ref.shape), dtype=torch.float32, device=means3D.device)
+        (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+         dL_drotations) = rp.RasterizeGaussiansDepthBackwardCUDA(
+            bg, means3D, radii, colors_precomp, scales, rotations, ctx.scale_modifier, cov3Ds_precomp, viewmatrix,
+            projmatrix, ctx.tanfovx, ctx.tanfovy, grad_out_color.contiguous(),
+            grad_depth.contiguous() if grad_depth is not None else None,
+            grad_alpha.contiguous() if grad_alpha is not None else None, sh, ctx.sh_degree, campos, geomBuffer,
+            ctx.num_rendered, binningBuffer, imgBuffer)
+        g = lambda t, ref: t if ref.numel() != 0 else None  # noqa: E731
+        return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
+                g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
+
+
 def rasterizeGaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
     """include/gaussian_rasterizer.h:79-101."""
     return GaussianRasterizerFunction.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                             cov3Ds_precomp, raster_settings)
+
+
+def rasterizeGaussiansWithDepth(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    """rasterizeGaussians plus the depth and alpha maps: -> (color (3,H,W), radii (P), depth (H,W), alpha (H,W))."""
+    return GaussianRasterizerDepthFunction.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                 cov3Ds_precomp, raster_settings)
 
 
 class GaussianRasterizer(torch.nn.Module):
@@ -102,6 +151,19 @@ class GaussianRasterizer(torch.nn.Module):
         color, radii = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                           cov3D_precomp, self.raster_settings_)
         return color, radii
+
+    def forward_with_depth(self, means3D, means2D, opacities, has_shs, has_colors_precomp, has_scales, has_rotations,
+                           has_cov3D_precomp, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
+        """forward() plus the depth map (sum z alpha T) and alpha map (1 - T_final): -> (color, radii, depth, alpha)."""
+        self._check(has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp)
+        e = self._absent(means3D)
+        shs = shs if has_shs else e
+        colors_precomp = colors_precomp if has_colors_precomp else e
+        scales = scales if has_scales else e
+        rotations = rotations if has_rotations else e
+        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        return rasterizeGaussiansWithDepth(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                           self.raster_settings_)
 
     def visible_filter(self, means3D, has_scales, has_rotations, has_cov3D_precomp, scales=None, rotations=None,
                        cov3D_precomp=None):

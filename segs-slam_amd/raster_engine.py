@@ -49,11 +49,16 @@ class RasterEngine:
     resident=True uses the no-host-sync entry points (segs_rasterize_*_resident): the first forward goes through the
     synchronising reference-shaped call to learn R, later calls run with capacity = 1.3 R + slack and only read the
     status words back asynchronously; `check()` (called at the start of the next forward) raises the capacity and
-    reports an overflow if R ever outgrew it."""
+    reports an overflow if R ever outgrew it.
+
+    render_depth=True: every forward also fills out_depth (sum z alpha T) and out_alpha (1 - T_final), both (H, W) and
+    allocated here once, through the `_depth` twins of the entry points; backward() then takes their gradients too."""
 
     def __init__(self, P: int, width: int, height: int, device="cuda:0", resident: bool = False,
-                 skip_nonpositive_opacity: bool = False, keep_dead_instances: bool = False, want_cov3D_grad: bool = False):
+                 skip_nonpositive_opacity: bool = False, keep_dead_instances: bool = False, want_cov3D_grad: bool = False,
+                 render_depth: bool = False):
         self.resident = bool(resident)
+        self.render_depth = bool(render_depth)
         # SEGS_RASTER_SKIP_NONPOSITIVE_OPACITY (segs_raster.h): candidate-domain inputs of segs_neural_forward
         # SEGS_RASTER_KEEP_DEAD_INSTANCES: resident forwards bin the reference's full bounding squares (R == R_reference)
         self.flags = (1 if skip_nonpositive_opacity else 0) | (2 if keep_dead_instances else 0)
@@ -72,6 +77,9 @@ class RasterEngine:
         self.device = torch.device(device)
         f = dict(dtype=torch.float32, device=self.device)
         self.out_color = torch.zeros((3, self.H, self.W), **f)
+        self.out_depth = torch.zeros((self.H, self.W), **f) if self.render_depth else None
+        self.out_alpha = torch.zeros((self.H, self.W), **f) if self.render_depth else None
+        self._depth_out = _capi.DepthOutputs(self.out_depth.data_ptr(), self.out_alpha.data_ptr()) if self.render_depth else None
         self.radii = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
         # (+4 floats behind the bucket: keyframe_parallel.BucketExchange lets the overflow word ride there in a dense exchange)
         self.grads_flat = torch.zeros((FLOATS_PER_GAUSSIAN * self.P + 4,), **f)[:FLOATS_PER_GAUSSIAN * self.P]
@@ -159,11 +167,15 @@ class RasterEngine:
                  scale_modifier):
         if self.resident and self.capacity > 0:
             self._lib.segs_raster_set_status_mirror(C.c_void_p(self._status_host.data_ptr()))
-            st = self._lib.segs_rasterize_forward_resident(
-                p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, 0, 0, p(bg), self.W, self.H, p(means3D),
-                None, p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix),
-                p(campos), float(tanfovx), float(tanfovy), p(self.out_color), p(self.radii), p(self._status), self._stream())
-            _capi.check(st, "segs_rasterize_forward_resident")
+            args = (p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, 0, 0, p(bg), self.W, self.H,
+                    p(means3D), None, p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix),
+                    p(projmatrix), p(campos), float(tanfovx), float(tanfovy), p(self.out_color), p(self.radii), p(self._status))
+            if self.render_depth:
+                st = self._lib.segs_rasterize_forward_resident_depth(*args, C.byref(self._depth_out), self._stream())
+                _capi.check(st, "segs_rasterize_forward_resident_depth")
+            else:
+                st = self._lib.segs_rasterize_forward_resident(*args, self._stream())
+                _capi.check(st, "segs_rasterize_forward_resident")
             if not torch.cuda.is_current_stream_capturing():
                 # R and the overflow word were stored into the pinned host words by the last binning kernel
                 self._status_event.record(torch.cuda.current_stream(self.device))
@@ -175,11 +187,15 @@ class RasterEngine:
         self._last_resident = False
         n = C.c_int(0)
         gcb, bcb, icb = self.geom.callback(), self.binning.callback(), self.img.callback()
-        st = self._lib.segs_rasterize_forward(
-            gcb, None, bcb, None, icb, None, self.P_active, 0, 0, p(bg), self.W, self.H, p(means3D),
-            None, p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix),
-            p(campos), float(tanfovx), float(tanfovy), 0, p(self.out_color), p(self.radii), self._stream(), C.byref(n))
-        _capi.check(st, "segs_rasterize_forward")
+        args = (gcb, None, bcb, None, icb, None, self.P_active, 0, 0, p(bg), self.W, self.H, p(means3D),
+                None, p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix),
+                p(campos), float(tanfovx), float(tanfovy), 0, p(self.out_color), p(self.radii))
+        if self.render_depth:
+            st = self._lib.segs_rasterize_forward_depth(*args, C.byref(self._depth_out), self._stream(), C.byref(n))
+            _capi.check(st, "segs_rasterize_forward_depth")
+        else:
+            st = self._lib.segs_rasterize_forward(*args, self._stream(), C.byref(n))
+            _capi.check(st, "segs_rasterize_forward")
         self.R = int(n.value)
         self.R_reference = self.R     # the reference's num_rendered (bounding-square duplication, rasterizer_impl.cu:70-111)
         self._last = (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
@@ -216,10 +232,14 @@ class RasterEngine:
         old_flags = self._lib.segs_raster_set_flags(self.flags)
         try:
             self._lib.segs_raster_set_status_mirror(C.c_void_p(self._status_host.data_ptr()))
-            st = self._lib.segs_rasterize_forward_resident_projected(p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P,
-                                                                     self.P_active, p(bg), self.W, self.H, p(self.out_color),
-                                                                     p(self._status), self._stream())
-            _capi.check(st, "segs_rasterize_forward_resident_projected")
+            args = (p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, p(bg), self.W, self.H,
+                    p(self.out_color), p(self._status))
+            if self.render_depth:
+                st = self._lib.segs_rasterize_forward_resident_projected_depth(*args, C.byref(self._depth_out), self._stream())
+                _capi.check(st, "segs_rasterize_forward_resident_projected_depth")
+            else:
+                st = self._lib.segs_rasterize_forward_resident_projected(*args, self._stream())
+                _capi.check(st, "segs_rasterize_forward_resident_projected")
         finally:
             self._lib.segs_raster_set_flags(old_flags)
             self._lib.segs_raster_set_status_mirror(None)
@@ -230,30 +250,46 @@ class RasterEngine:
         self._last_resident = True
         return self.out_color
 
-    def backward(self, dL_dout_color: torch.Tensor):
-        """Gradients land in self.grads (views of self.grads_flat), dL_dmean2D, dL_dcov3D."""
+    def backward(self, dL_dout_color: torch.Tensor, dL_ddepth: torch.Tensor = None, dL_dalpha: torch.Tensor = None):
+        """Gradients land in self.grads (views of self.grads_flat), dL_dmean2D, dL_dcov3D.  dL_ddepth / dL_dalpha (H, W; None =
+        zero) are the gradients of out_depth / out_alpha of a render_depth engine."""
         (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
          scale_modifier) = self._last
         assert dL_dout_color.is_contiguous() and dL_dout_color.dtype == torch.float32
+        depth_grads = None
+        if dL_ddepth is not None or dL_dalpha is not None:
+            if not self.render_depth:
+                raise ValueError("depth / alpha gradients need an engine made with render_depth=True")
+            for t in (dL_ddepth, dL_dalpha):
+                assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (self.H, self.W))
+            depth_grads = _capi.DepthGrads(dL_ddepth.data_ptr() if dL_ddepth is not None else None,
+                                           dL_dalpha.data_ptr() if dL_dalpha is not None else None)
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         pn = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         g = self.grads
         if getattr(self, "_last_resident", False):
-            st = self._lib.segs_rasterize_backward_resident(
-                p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, 0, 0, p(bg), self.W, self.H, p(means3D),
-                None, p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix), p(campos),
-                float(tanfovx), float(tanfovy), p(self.radii), p(dL_dout_color), p(self.dL_dmean2D), None,
-                p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]), p(g["rotations"]),
-                self._stream())
-            _capi.check(st, "segs_rasterize_backward_resident")
+            args = (p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, 0, 0, p(bg), self.W, self.H,
+                    p(means3D), None, p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix), p(campos),
+                    float(tanfovx), float(tanfovy), p(self.radii), p(dL_dout_color), p(self.dL_dmean2D), None,
+                    p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]), p(g["rotations"]))
+            if depth_grads is not None:
+                st = self._lib.segs_rasterize_backward_resident_depth(*args, C.byref(depth_grads), self._stream())
+                _capi.check(st, "segs_rasterize_backward_resident_depth")
+            else:
+                st = self._lib.segs_rasterize_backward_resident(*args, self._stream())
+                _capi.check(st, "segs_rasterize_backward_resident")
             return g
-        st = self._lib.segs_rasterize_backward(
-            self.P_active, 0, 0, self.R, p(bg), self.W, self.H, p(means3D), None, p(colors), p(scales), float(scale_modifier),
-            p(rotations), None, p(viewmatrix), p(projmatrix), p(campos), float(tanfovx), float(tanfovy), p(self.radii),
-            p(self.geom.tensor), p(self.binning.tensor), p(self.img.tensor), p(dL_dout_color), p(self.dL_dmean2D),
-            None, p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]),
-            p(g["rotations"]), self._stream())
-        _capi.check(st, "segs_rasterize_backward")
+        args = (self.P_active, 0, 0, self.R, p(bg), self.W, self.H, p(means3D), None, p(colors), p(scales), float(scale_modifier),
+                p(rotations), None, p(viewmatrix), p(projmatrix), p(campos), float(tanfovx), float(tanfovy), p(self.radii),
+                p(self.geom.tensor), p(self.binning.tensor), p(self.img.tensor), p(dL_dout_color), p(self.dL_dmean2D),
+                None, p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]),
+                p(g["rotations"]))
+        if depth_grads is not None:
+            st = self._lib.segs_rasterize_backward_depth(*args, C.byref(depth_grads), self._stream())
+            _capi.check(st, "segs_rasterize_backward_depth")
+        else:
+            st = self._lib.segs_rasterize_backward(*args, self._stream())
+            _capi.check(st, "segs_rasterize_backward")
         return g
 
 

@@ -10,6 +10,10 @@ as the reference, so the parity tests read like calls into the reference:
   RasterizeGaussiansfilterCUDA    src/rasterize_points.cu:216-280
   RasterizeGaussiansprojectCUDA   src/rasterize_points.cu:282-363
 
+and, with no reference counterpart, the pair that also renders a depth and an alpha map (segs_rasterize_*_depth):
+
+  RasterizeGaussiansDepthCUDA / RasterizeGaussiansDepthBackwardCUDA
+
 torch is plumbing only here (device memory + current stream); every kernel is in csrc/.
 """
 from __future__ import annotations
@@ -132,6 +136,92 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                 _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
                 _ptr(dL_drotations) if has_sr else None, _stream(dev))
         _capi.check(st, "segs_rasterize_backward")
+    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+def _depth_grad_ptr(t, H, W, name):
+    if t is None or t.numel() == 0:
+        return None
+    if tuple(t.shape) != (H, W):
+        raise RuntimeError(f"{name} must be (H, W) = ({H}, {W}), got {tuple(t.shape)}")
+    _require_gpu(t, name)
+    return t
+
+
+def RasterizeGaussiansDepthCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                                viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                                prefiltered):
+    """RasterizeGaussiansCUDA plus the depth map sum z alpha T and the alpha map 1 - T_final of the same contributors
+    (include/segs_raster.h, segs_rasterize_forward_depth).
+    -> (num_rendered, out_color(3,H,W), radii(P), out_depth(H,W), out_alpha(H,W), geomBuffer, binningBuffer, imgBuffer)."""
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    _require_gpu(means3D, "means3D")
+    dev = means3D.device
+    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    mk = torch.empty if P != 0 else torch.zeros
+    out_color = mk((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
+    out_depth = mk((H, W), dtype=torch.float32, device=dev)
+    out_alpha = mk((H, W), dtype=torch.float32, device=dev)
+    radii = mk((P,), dtype=torch.int32, device=dev)
+    geom, binning, img = _ResizableBuffer(dev), _ResizableBuffer(dev), _ResizableBuffer(dev)
+    rendered = 0
+    if P != 0:  # as RasterizeGaussiansCUDA: P == 0 leaves zero maps
+        M = int(sh.size(1)) if sh.numel() != 0 else 0
+        keep = [_f32c(t) for t in (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp,
+                                   viewmatrix, projmatrix, campos)]
+        bg, m3, shc, col, opa, sca, rot, cov, view, proj, cam = keep
+        n = C.c_int(0)
+        gcb, bcb, icb = geom.callback(), binning.callback(), img.callback()
+        dout = _capi.DepthOutputs(out_depth.data_ptr(), out_alpha.data_ptr())
+        with torch.cuda.device(dev):
+            st = _capi.lib().segs_rasterize_forward_depth(
+                gcb, None, bcb, None, icb, None, P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(shc),
+                _ptr(col), _ptr(opa), _ptr(sca), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj),
+                _ptr(cam), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(out_color), _ptr(radii),
+                C.byref(dout), _stream(dev), C.byref(n))
+        _capi.check(st, "segs_rasterize_forward_depth")
+        rendered = int(n.value)
+    return rendered, out_color, radii, out_depth, out_alpha, geom.tensor, binning.tensor, img.tensor
+
+
+def RasterizeGaussiansDepthBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                                        viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_alpha,
+                                        sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer):
+    """RasterizeGaussiansBackwardCUDA plus the gradients of the depth and alpha maps (H, W); either may be None or a
+    0-element tensor (zero).  Same return tuple."""
+    _require_gpu(means3D, "means3D")
+    dev = means3D.device
+    P, H, W = int(means3D.size(0)), int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    opts = dict(dtype=torch.float32, device=dev)
+    dL_dmeans3D = torch.empty((P, 3), **opts)
+    dL_dmeans2D = torch.empty((P, 3), **opts)
+    dL_dcolors = torch.empty((P, NUM_CHANNELS), **opts)
+    dL_dopacity = torch.empty((P, 1), **opts)
+    dL_dcov3D = torch.empty((P, 6), **opts)
+    dL_dsh = torch.zeros((P, M, 3), **opts)
+    has_sr = scales.numel() != 0
+    dL_dscales = torch.empty((P, 3), **opts) if has_sr else torch.zeros((P, 3), **opts)
+    dL_drotations = torch.empty((P, 4), **opts) if has_sr else torch.zeros((P, 4), **opts)
+    gD = _depth_grad_ptr(dL_dout_depth, H, W, "dL_dout_depth")
+    gA = _depth_grad_ptr(dL_dout_alpha, H, W, "dL_dout_alpha")
+    gD, gA = (_f32c(t) if t is not None else None for t in (gD, gA))
+    if P != 0:
+        keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
+                                   projmatrix, campos, dL_dout_color)]
+        bg, m3, shc, col, sca, rot, cov, view, proj, cam, dL = keep
+        rad = radii.contiguous()
+        dg = _capi.DepthGrads(gD.data_ptr() if gD is not None else None, gA.data_ptr() if gA is not None else None)
+        with torch.cuda.device(dev):
+            st = _capi.lib().segs_rasterize_backward_depth(
+                P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sca),
+                float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx),
+                float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL),
+                _ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dmeans3D),
+                _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
+                _ptr(dL_drotations) if has_sr else None, C.byref(dg), _stream(dev))
+        _capi.check(st, "segs_rasterize_backward_depth")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
