@@ -78,11 +78,12 @@ int segs_l1_ssim_loss(const float* img1, const float* img2, int H, int W, float 
 
 /* ---- Frequency regulariser of the mapper loss (src/gaussian_mapper.cpp:930-945) ----------------------------------------
  * loss_utils::multi_scale_loss / high_frequency_loss (include/loss_utils.h:126-165, 216-237):
- *     freq = lambda_high * sum_s  s * mean( | |fft2(resize_s(image))| - |fft2(resize_s(gt))| | ),   s = 1, 1/2, 1/4
+ *     freq = lambda_high * sum_s  s * mean( | |fft2(resize_s(image))| - |fft2(resize_s(gt))| | ),   s = 1 / 2^i, i < scale_num
  * (without Mapper.use_multi_resolution: the s = 1 term alone).  resize_s is torch's bilinear interpolate with
  * align_corners = false and recompute_scale_factor = true, i.e. to floor(size * s) with scale = in / out.  The reference's
- * frequency mask is a no-op for real image sizes and low_freq_loss has a zero gradient (pinned by
- * tests/golden/loss_reference.npz), so this is the whole regulariser.
+ * frequency mask, indexed on (channel, row), is a no-op except at levels 5 to 7 rows high, where segs_freq_spectrum_loss
+ * applies it as the reference does; low_freq_loss has a zero gradient (pinned by
+ * tests/golden/loss_reference.npz and loss_reference_scales.npz), so this is the whole regulariser.
  *
  * The FFTs stay library calls of the caller (hipFFT through torch.fft / torch::fft, like the reference); these entry points
  * are everything around them, one launch each for all scales ("levels"; at most SEGS_FREQ_MAX_LEVELS):
@@ -90,14 +91,15 @@ int segs_l1_ssim_loss(const float* img1, const float* img2, int H, int W, float 
  *                                  of the image's own size is the image: its buffer is not written and may be NULL);
  *   2. caller: spectrum[l] = rfft2(level l)  -- (C, h_l, w_l/2+1) interleaved complex64, unnormalised;
  *   3. segs_freq_spectrum_loss     *freq_loss_out = sum_l level_weight[l] * sum_k m_k | |G_k| - target_magnitude[l][k] |
- *                                  (m_k = 2 for the columns that stand for their mirror image too, else 1), added to
+ *                                  (m_k = 2 for the columns that stand for their mirror image too, else 1; entries that
+ *                                  the reference's mask zeroes count 0), added to
  *                                  *loss_inout if non-NULL; spectrum[l] <- level_weight[l] * sign(|G|-|T|) * G/|G| in place.
  *                                  level_weight[l] = lambda_high * s_l / (C h_l w_l);
  *   4. caller: level_grad[l] = irfft2(spectrum[l], size (h_l,w_l)) WITHOUT the 1/(h w) normalisation (norm = "forward");
  *   5. segs_freq_pyramid_backward_add   dL_dimage += sum_l resize_l^T(level_grad[l])   (plain add for a full-size level).
  * target_magnitude[l] = |rfft2(resize_l(gt))| is constant per keyframe: segs_freq_pyramid + rfft2 + segs_spectrum_magnitude
  * once, then cached by the host.  temp: segs_freq_temp_bytes(...) bytes. */
-#define SEGS_FREQ_MAX_LEVELS 4
+#define SEGS_FREQ_MAX_LEVELS 8   /* Mapper.scale_num of the shipped configurations: 2 to 5 */
 int segs_freq_pyramid(const float* image, int C, int H, int W, int nlevels, const int* level_h, const int* level_w,
                       float* const* level_out, void* stream);
 int segs_spectrum_magnitude(const float* spectrum, size_t n_complex, float* magnitude, void* stream);

@@ -2,16 +2,18 @@
 // Reference: loss_utils::high_frequency_loss / multi_scale_loss (include/loss_utils.h:126-165, 216-237) as used at
 // src/gaussian_mapper.cpp:930-945:
 //     loss += lambda_high * sum_s  s * mean( | |fft2(resize_s(image))| - |fft2(resize_s(gt))| | ),   s in {1, 1/2, 1/4}
-// (the "high-pass" mask of :139-140 is indexed on (channel, row) and therefore all ones for any real image size, and
-// fftshift does not change a mean -- tests/golden/loss_reference.npz, generated from the reference's compiled header,
-// pins both statements).  The reference evaluates this with ~10 ATen kernels per scale and direction plus autograd.
+// (the "high-pass" mask of :139-140 is indexed on (channel, row) and therefore all ones except at levels 5 to 7 rows high,
+// where it zeroes whole rows of one channel's spectrum -- ref_mask_box, applied by freq_spectrum_kernel; fftshift does not
+// change a mean -- tests/golden/loss_reference.npz and loss_reference_scales.npz, generated from the reference's compiled
+// header, pin both statements).  The reference evaluates this with ~10 ATen kernels per scale and direction plus autograd.
 // Here the two library transforms per scale (real-to-complex forward, complex-to-real inverse; hipFFT through the
 // caller's tensor library, as in the reference) are the only image-sized passes besides three small kernels:
 //   freq_pyramid_fwd_kernel   image -> the down-scaled copies (bilinear, align_corners = false), all scales in one launch
 //   freq_spectrum_kernel      G = rfft2(level):  loss partial  w * m(kx) * | |G| - |T| |,   G <- w * sign(|G| - |T|) * G / |G|
 //                             in place, all scales in one launch; |T| of the target is cached by the host per keyframe
 //   freq_pyramid_bwd_kernel   dL/dimage += sum_s  resize_s^T( irfft2_unnormalised(G_s) )       (gather form, no atomics)
-// When H and W are multiples of 4 and the scales are 1, 1/2, 1/4 (every shipped configuration: 1200x680, 640x480), the
+// When H and W are multiples of 4 and the scales are 1, 1/2, 1/4 (Mapper.scale_num 3, most shipped configurations: 1200x680,
+// 640x480; other scale counts, up to SEGS_FREQ_MAX_LEVELS, take the per-scale path), the
 // half- and quarter-size copies are exact 2-tap decimations (src = s d + (s - 1)/2: taps s d + s/2 - 1 and s d + s/2, weights
 // 1/2), and the spectrum of a decimated signal is an alias fold of the full-size one:
 //     Y_s[k] = 1/s^2 sum_{a,b < s}  X[ky + a H/s, kx + b W/s] * C_s(ky + a H/s; H) * C_s(kx + b W/s; W),
@@ -32,6 +34,9 @@
 #include <cstdint>
 #include <cstdlib>
 #include <initializer_list>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <vector>
 #include "../../include/segs_raster.h"
 #include "kernels.h"
@@ -79,8 +84,9 @@ __global__ void __launch_bounds__(256) freq_pyramid_fwd_kernel(const float* __re
 }
 
 struct SpecLevels {
-  int n;
-  int w[MAXL];               // full width of the level (the half spectrum has w/2 + 1 columns)
+  int n, C;
+  int h[MAXL], w[MAXL];      // size of the level (the half spectrum has w/2 + 1 columns)
+  int mask_c0[MAXL], mask_c1[MAXL], mask_r0[MAXL], mask_r1[MAXL];   // the reference's zeroed box (ref_mask_box), fftshifted
   float2* spec[MAXL];        // (C, h, w/2+1) complex, in/out
   const float* tmag[MAXL];   // |T|, same shape, real
   float weight[MAXL];        // lambda * scale / (C h w)
@@ -109,11 +115,26 @@ __global__ void __launch_bounds__(256) freq_spectrum_kernel(SpecLevels lv, float
     const float2 g = lv.spec[l][e];
     const float m = sqrtf(g.x * g.x + g.y * g.y);
     const float d = m - lv.tmag[l][e];
-    const float mult = (kx == 0 || (2 * kx == w)) ? 1.f : 2.f;
+    const bool self_mirror = kx == 0 || 2 * kx == w;
+    float mult = self_mirror ? 1.f : 2.f, keep = 1.f;
+    if (lv.mask_c1[l] > lv.mask_c0[l]) {
+      // a level whose (channel, row) box of the reference's high-pass mask is not empty: the full-spectrum entries (c, ky, kx)
+      // and (c, -ky, -kx) that this stored one stands for count with their own mask values m0, m1; the gradient is the inverse
+      // transform of the Hermitian part of the masked coefficients, i.e. this entry scaled by (m0 + m1) / 2
+      const int h = lv.h[l], ky = (e / wc) % h, c = e / ((unsigned)wc * h);
+      const int cs = (c + lv.C / 2) % lv.C;
+      auto kept = [&](int row) {
+        const int rs = (row + h / 2) % h;
+        return (cs >= lv.mask_c0[l] && cs < lv.mask_c1[l] && rs >= lv.mask_r0[l] && rs < lv.mask_r1[l]) ? 0.f : 1.f;
+      };
+      const float m0 = kept(ky), m1 = kept(ky ? h - ky : 0);
+      mult = self_mirror ? m0 : m0 + m1;
+      keep = 0.5f * (m0 + m1);
+    }
     const float wl = lv.weight[l];
     term = wl * mult * fabsf(d);
     const float s = d > 0.f ? wl : (d < 0.f ? -wl : 0.f);
-    const float k = m > 0.f ? s / m : 0.f;
+    const float k = m > 0.f ? keep * s / m : 0.f;
     lv.spec[l][e] = make_float2(k * g.x, k * g.y);
   }
   const float sum = block_sum_256(term, red);
@@ -338,6 +359,44 @@ __global__ void __launch_bounds__(256) add_kernel(float* __restrict__ dst, const
 
 int bad(const char* what) { return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, what); }
 
+// The reference's high-pass mask (loss_utils.h:126-145): ones, with the box Slice(crow - r, crow + r) x Slice(ccol - r, ccol + r)
+// zeroed on dimensions (0, 1) of the fftshifted (C, h, w) spectrum -- channel and ROW, not row and column -- with crow = h / 2,
+// ccol = w / 2, r = (int)(0.4f * min(h, w) / 2).  The channel slice is empty unless h / 2 - r < C, i.e. for levels 5 to 7 rows
+// high at C = 3 (e.g. 48x64 at scale 1/8: 6x8); there it zeroes whole spectrum rows of one channel.  Python slice bounds.
+void slice_bounds(int start, int stop, int n, int& lo, int& hi) {
+  if (start < 0) start += n;
+  if (stop < 0) stop += n;
+  lo = start < 0 ? 0 : (start > n ? n : start);
+  hi = stop < 0 ? 0 : (stop > n ? n : stop);
+  if (hi < lo) hi = lo;
+}
+// false when the mask is all ones; else its box in fftshifted coordinates: channels [c0, c1), rows [r0, r1)
+bool ref_mask_box(int C, int h, int w, int& c0, int& c1, int& r0, int& r1) {
+  const int crow = h / 2, ccol = w / 2, r = (int)(0.4f * (float)(h < w ? h : w) / 2.f);
+  slice_bounds(crow - r, crow + r, C, c0, c1);
+  slice_bounds(ccol - r, ccol + r, h, r0, r1);
+  if (c1 > c0 && r1 > r0) return true;
+  c0 = c1 = r0 = r1 = 0;
+  return false;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of a process-global kernel is shared by every plan that launches it: a plan
+// created later for a smaller image must not lower the limit an earlier, larger plan still launches with ("one plan per image
+// size", several alive at once).  So the attribute only ever grows: a process-wide maximum per (kernel, device), raised under
+// a mutex.
+hipError_t raise_lds_limit(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, int> limit;
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  int& cur = limit[{kernel, dev}];
+  if (bytes <= cur) return hipSuccess;
+  if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
+  cur = bytes;
+  return hipSuccess;
+}
+
 // ---- hipFFT, bound at run time --------------------------------------------------------------------------------------
 // The process that loads this library has, as a rule, a tensor library in it that already carries a hipFFT (PyTorch-ROCm
 // bundles libhipfft.so.0 next to its HIP runtime).  Linking a second copy in through DT_NEEDED could bind another HIP runtime;
@@ -441,9 +500,12 @@ int segs_freq_spectrum_loss(int C, int nlevels, const int* level_h, const int* l
   SpecLevels lv{};
   unsigned total = 0;
   lv.n = nlevels;
+  lv.C = C;
   for (int l = 0; l < nlevels; l++) {
     if (level_h[l] <= 0 || level_w[l] <= 0 || !spectrum[l] || !target_magnitude[l]) return bad("segs_freq_spectrum_loss: bad level");
+    lv.h[l] = level_h[l];
     lv.w[l] = level_w[l];
+    ref_mask_box(C, level_h[l], level_w[l], lv.mask_c0[l], lv.mask_c1[l], lv.mask_r0[l], lv.mask_r1[l]);
     lv.spec[l] = reinterpret_cast<float2*>(spectrum[l]);
     lv.tmag[l] = target_magnitude[l];
     lv.weight[l] = level_weight[l];
@@ -506,6 +568,10 @@ int segs_freq_plan_create(int H, int W, int nscales, const float* scales, float 
     p->weight[l] = lambda_high * scales[l] / (3.f * (float)p->h[l] * (float)p->w[l]);   // loss_utils.h:235: scale * mean(...)
   }
   p->folded = nscales == 3 && scales[0] == 1.f && scales[1] == 0.5f && scales[2] == 0.25f && H % 4 == 0 && W % 4 == 0;
+  for (int l = 0; l < nscales && p->folded; l++) {     // (the fold evaluates unmasked levels only: tiny images take the per-scale path)
+    int c0, c1, r0, r1;
+    if (ref_mask_box(3, p->h[l], p->w[l], c0, c1, r0, r1)) p->folded = false;
+  }
   // SEGS_FREQ_HIPFFT=1: keep the library transforms (A/B measurements, and the fallback's tests)
   static const bool force_library = [] { const char* e = getenv("SEGS_FREQ_HIPFFT"); return e && e[0] == '1'; }();
   p->own_fft = p->folded && !force_library && rfft::factorize(W / 2, p->st_rows) && rfft::factorize(H, p->st_cols) &&
@@ -553,9 +619,9 @@ int segs_freq_plan_create(int H, int W, int nscales, const float* scales, float 
     for (int n = 0; n < H; n++) th[n] = make_float2((float)std::cos(two_pi * n / H), (float)-std::sin(two_pi * n / H));
     if (hipMemcpy(p->root_w, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(p->root_h, th.data(), th.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(rfft::rows_r2c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rfft::rows_lds_bytes(W)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(rfft::rows_c2r_add_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rfft::rows_lds_bytes(W)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(rfft::cols_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rfft::cols_lds_bytes(H)) != hipSuccess) {
+        raise_lds_limit(reinterpret_cast<const void*>(rfft::rows_r2c_kernel), (int)rfft::rows_lds_bytes(W)) != hipSuccess ||
+        raise_lds_limit(reinterpret_cast<const void*>(rfft::rows_c2r_add_kernel), (int)rfft::rows_lds_bytes(W)) != hipSuccess ||
+        raise_lds_limit(reinterpret_cast<const void*>(rfft::cols_kernel), (int)rfft::cols_lds_bytes(H)) != hipSuccess) {
       segs_freq_plan_destroy(p);
       return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, "segs_freq_plan_create: could not set up the transform kernels");
     }
@@ -599,16 +665,27 @@ static unsigned fold_threads(const segs_freq_plan* p) {
   return p->own_fft ? 3u * ((w4 + 7u) / 8u) * ((h4 + 7u) / 8u) * 64u : 3u * h4 * w4;
 }
 
-// own transforms of a folded plan (real_fft.h): image (3,H,W) -> half spectrum (3,H,W/2+1), and the way back, added into dL
-static void own_forward(const segs_freq_plan* p, const float* image, float2* spec, hipStream_t st) {
+// own transforms of a folded plan (real_fft.h): image (3,H,W) -> half spectrum (3,H,W/2+1), and the way back, added into dL.
+// These launches ask for up to ~150 KB of dynamic LDS, so they are the ones that can be refused at launch.  Each launch's
+// status is read right after it (hipGetLastError), so a refused transform comes back as an error status of
+// segs_freq_target / segs_freq_loss whether or not a later successful call would overwrite the runtime's last error.
+static int launch_status(const char* what) {
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SEGS_OK : segs::set_hip_error(e, what);
+}
+static int own_forward(const segs_freq_plan* p, const float* image, float2* spec, hipStream_t st) {
   const int rows = 3 * p->H, wc = p->W / 2 + 1;
   rfft::rows_r2c_kernel<<<(rows + rfft::ROWS_PER_WG - 1) / rfft::ROWS_PER_WG, rfft::ROW_THREADS, rfft::rows_lds_bytes(p->W), st>>>(image, spec, rows, p->H, p->W, p->st_rows, p->root_w);
+  if (int rc = launch_status("rfft::rows_r2c_kernel")) return rc;
   rfft::cols_kernel<<<dim3(rfft::tiles_of(wc), 3), rfft::COL_THREADS, rfft::cols_lds_bytes(p->H), st>>>(spec, p->H, wc, p->st_cols, p->root_h, -1.f, nullptr, 0, nullptr, nullptr);
+  return launch_status("rfft::cols_kernel (forward)");
 }
-static void own_inverse_add(const segs_freq_plan* p, float2* spec, float* dL, hipStream_t st, int npartial, float* freq_loss_out, float* loss_inout) {
+static int own_inverse_add(const segs_freq_plan* p, float2* spec, float* dL, hipStream_t st, int npartial, float* freq_loss_out, float* loss_inout) {
   const int rows = 3 * p->H, wc = p->W / 2 + 1;
   rfft::cols_kernel<<<dim3(rfft::tiles_of(wc), 3), rfft::COL_THREADS, rfft::cols_lds_bytes(p->H), st>>>(spec, p->H, wc, p->st_cols, p->root_h, +1.f, p->partial, npartial, freq_loss_out, loss_inout);
+  if (int rc = launch_status("rfft::cols_kernel (inverse)")) return rc;
   rfft::rows_c2r_add_kernel<<<(rows + rfft::ROWS_PER_WG - 1) / rfft::ROWS_PER_WG, rfft::ROW_THREADS, rfft::rows_lds_bytes(p->W), st>>>(spec, dL, rows, p->H, p->W, p->st_rows, p->root_w);
+  return launch_status("rfft::rows_c2r_add_kernel");
 }
 
 // down-scaled copies of `image` for the generic path; returns the per-level source pointers in src[]
@@ -623,8 +700,9 @@ int segs_freq_target(segs_freq_plan* p, const float* gt, float* target_out, void
   const HipFft& f = hipfft();
   hipStream_t st = (hipStream_t)stream;
   if (p->folded) {
-    if (p->own_fft) own_forward(p, gt, reinterpret_cast<float2*>(p->spec[0]), st);
-    else if (f.SetStream(p->r2c[0], st) != HIPFFT_SUCCESS ||
+    if (p->own_fft) {
+      if (int rc = own_forward(p, gt, reinterpret_cast<float2*>(p->spec[0]), st)) return rc;
+    } else if (f.SetStream(p->r2c[0], st) != HIPFFT_SUCCESS ||
         f.ExecR2C(p->r2c[0], const_cast<float*>(gt), reinterpret_cast<hipfftComplex*>(p->spec[0])) != HIPFFT_SUCCESS)
       return fft_fail("segs_freq_target: hipfftExecR2C failed");
     const unsigned nthr = fold_threads(p);
@@ -652,8 +730,9 @@ int segs_freq_loss(segs_freq_plan* p, const float* image, const float* target, f
   hipStream_t st = (hipStream_t)stream;
   const size_t npix = (size_t)3 * p->H * p->W;
   if (p->folded) {
-    if (p->own_fft) own_forward(p, image, reinterpret_cast<float2*>(p->spec[0]), st);
-    else {
+    if (p->own_fft) {
+      if (int rc = own_forward(p, image, reinterpret_cast<float2*>(p->spec[0]), st)) return rc;
+    } else {
     if (f.SetStream(p->r2c[0], st) != HIPFFT_SUCCESS || f.SetStream(p->c2r[0], st) != HIPFFT_SUCCESS) return fft_fail("segs_freq_loss: hipfftSetStream failed");
     if (f.ExecR2C(p->r2c[0], const_cast<float*>(image), reinterpret_cast<hipfftComplex*>(p->spec[0])) != HIPFFT_SUCCESS)
       return fft_fail("segs_freq_loss: hipfftExecR2C failed");
@@ -664,7 +743,7 @@ int segs_freq_loss(segs_freq_plan* p, const float* image, const float* target, f
                                                   const_cast<float*>(target + p->toff[2]), p->weight[0], p->weight[1], p->weight[2], p->partial, p->own_fft);
     if (p->own_fft) {
       // (the column pass folds the loss partials on its way, the row pass adds into dL/dimage itself)
-      own_inverse_add(p, reinterpret_cast<float2*>(p->spec[1]), dL_inout, st, (int)nblk, freq_loss_out, loss_inout);
+      if (int rc = own_inverse_add(p, reinterpret_cast<float2*>(p->spec[1]), dL_inout, st, (int)nblk, freq_loss_out, loss_inout)) return rc;
     } else {
       freq_finish_kernel<<<1, 1024, 0, st>>>(p->partial, (int)nblk, freq_loss_out, loss_inout);
       if (f.ExecC2R(p->c2r[0], reinterpret_cast<hipfftComplex*>(p->spec[1]), p->grad[0]) != HIPFFT_SUCCESS)

@@ -32,6 +32,9 @@ import torch
 
 from . import _capi
 
+# SEGS_FREQ_MAX_LEVELS of include/segs_train.h: the most scales one evaluation takes (tests/test_capi_cpu.py keeps the two equal)
+MAX_LEVELS = 8
+
 
 def level_sizes(H: int, W: int, scales: Sequence[float]) -> List[Tuple[int, int]]:
     """Output sizes of F.interpolate(scale_factor=s, recompute_scale_factor=True): floor(size * s) in double."""
@@ -56,7 +59,7 @@ class FusedFrequencyLoss:
         self.scales = tuple(float(s) for s in scales) if multi_resolution else (1.0,)
         self.sizes = level_sizes(self.H, self.W, self.scales)
         n = len(self.sizes)
-        if n > 4 or any(h <= 0 or w <= 0 for h, w in self.sizes):
+        if n > MAX_LEVELS or any(h <= 0 or w <= 0 for h, w in self.sizes):
             raise ValueError(f"unsupported scales {self.scales} for {self.W}x{self.H}")
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.value = torch.zeros(1, **f32)

@@ -32,6 +32,25 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_capi.SYMBOLS) == declared
 
 
+def test_frequency_level_limit_matches_the_header():
+    """FusedFrequencyLoss refuses scale counts by the library's SEGS_FREQ_MAX_LEVELS (include/segs_train.h), and that limit
+    takes every Mapper.scale_num of the shipped configurations with the frequency regulariser on (2 to 5)."""
+    import json
+    from segs_slam_amd import frequency_loss, mapper_config as mc
+    text = open(os.path.join(ROOT, "include", "segs_train.h")).read()
+    m = re.search(r"^#define\s+SEGS_FREQ_MAX_LEVELS\s+(\d+)\b", text, flags=re.M)
+    assert m, "SEGS_FREQ_MAX_LEVELS not found"
+    assert frequency_loss.MAX_LEVELS == int(m.group(1))
+    with open(os.path.join(ROOT, "tests", "golden", "mapper_cfg_values.json")) as f:
+        shipped = json.load(f)
+    counts = {mc.mapper_config_from_values(v, k).scale_num for k, v in shipped.items()
+              if mc.mapper_config_from_values(v, k).use_frequency_regularization}
+    assert counts == {2, 3, 4, 5} and max(counts) <= frequency_loss.MAX_LEVELS
+    # and their smallest levels exist at the shipped image sizes (a zero-sized level is refused)
+    for H, W in ((680, 1200), (480, 640), (480, 752)):
+        assert all(h > 0 and w > 0 for h, w in frequency_loss.level_sizes(H, W, [1.0 / 2 ** i for i in range(max(counts))]))
+
+
 def test_scratch_size_queries_are_monotone_and_aligned():
     from segs_slam_amd import _capi
     lib = _capi.lib()

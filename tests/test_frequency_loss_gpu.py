@@ -38,21 +38,25 @@ def _check_against_float64(img, gt, lam, scales, val, got):
     autograd).  Nothing else is adjusted: after that the stated bar applies to every entry of dL/dimage -- 1e-4 relative
     + 1e-5 of its largest entry -- and the value to 1e-5 relative.  Returns (near ties, signs taken from the device).
 
-    Sizes that are not multiples of 4 resize with non-trivial bilinear weights: those copies are taken with float32
-    F.interpolate on the device, the op the reference runs (ATen forms the source coordinate scale * (dst + 0.5) - 0.5 in
-    float32 for float32 images), and its own backward carries the level gradients to the image; exact 2x / 4x resizes
-    (weights 1/2 in any precision) run in float64 throughout."""
+    A downscale by 2^k (align_corners = false, scale = in / out = 2^k) takes two taps at weight 1/2 -- in any precision -- iff
+    H and W are multiples of 2^k; such levels run in float64 throughout.  The others resize with non-trivial bilinear weights
+    (e.g. 1200x680 at 1/16: 75x42, 680/16 floored): those copies are taken with float32 F.interpolate on the device, the op the
+    reference runs (ATen forms the source coordinate scale * (dst + 0.5) - 0.5 in float32 for float32 images), and its own
+    backward carries the level gradients to the image."""
+    from segs_slam_amd import loss_utils, frequency_loss
     H, W = img.shape[-2:]
-    exact = H % 4 == 0 and W % 4 == 0
-    src = img.double() if exact else img
-    a = src.clone().requires_grad_(True)
-    levels = [_interp64(a, s) for s in scales]
+    for h, w in frequency_loss.level_sizes(H, W, scales):   # the reference's (channel, row) mask is all ones at these levels
+        assert not range(3)[loss_utils._centre_box(h, w, 0.4)[0]], (h, w)
+    exact = [H % round(1.0 / s) == 0 and W % round(1.0 / s) == 0 for s in scales]
+    a64, a32 = img.double().requires_grad_(True), img.clone().requires_grad_(True)
+    levels = [_interp64(a64 if ex else a32, s) for s, ex in zip(scales, exact)]
     leaves = [x.detach().double().requires_grad_(True) for x in levels]
-    tgt = [_interp64(gt.double() if exact else gt, s).double() for s in scales]
+    tgt = [_interp64(gt.double() if ex else gt, s).double() for s, ex in zip(scales, exact)]
 
     def to_image(level_grads):
-        g = torch.autograd.grad(levels, a, [x.to(lv.dtype) for x, lv in zip(level_grads, levels)], retain_graph=True)[0]
-        return g.double()
+        gs = torch.autograd.grad(levels, [a64, a32], [x.to(lv.dtype) for x, lv in zip(level_grads, levels)], retain_graph=True,
+                                 allow_unused=True)
+        return sum(g.double() for g in gs if g is not None)
 
     spectra, total = [], 0.0
     for s, lv, t in zip(scales, leaves, tgt):
@@ -109,6 +113,91 @@ def test_fused_frequency_loss_matches_float64_mirror_at_step_sizes(size, multi, 
     print(f"{W}x{H} multi={multi} torch_fft={torch_fft}: {ties} near ties, {taken} took the device's sign")
 
 
+def _own_transform_size(n):
+    """csrc/real_fft.h transforms lengths whose prime factors are in {2, 3, 5, 17}."""
+    for p in (2, 3, 5, 17):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+# Mapper.scale_num of the shipped configurations with the regulariser on: 3 (folded where H, W are multiples of 4), 2, 4, 5 (the
+# per-scale path); 1 = high_frequency_loss alone.  Sizes: the shipped 1200x680, 640x480 and EuRoC's 752x480 (folded at 3 scales,
+# but W/2 = 376 = 8.47: the vendor library's transforms), and two odd ones.  Scale counts 1 and 3 at the other sizes are
+# test_fused_frequency_loss_matches_float64_mirror_at_step_sizes.
+_SCALE_SIZES = [(680, 1200), (480, 640), (480, 752), (187, 333), (64, 72)]
+_SCALE_CASES = [(sz, n, tf) for tf in (False, True) for n in (1, 2, 3, 4, 5) for sz in _SCALE_SIZES
+                if n in (2, 4, 5) or sz == (480, 752)]
+
+
+@pytest.mark.parametrize("size,nscales,torch_fft", _SCALE_CASES,
+                         ids=[f"{w}x{h}-n{n}-{'torch_fft' if tf else 'plan'}" for (h, w), n, tf in _SCALE_CASES])
+def test_fused_frequency_loss_matches_float64_mirror_at_every_scale_count(size, nscales, torch_fft):
+    """test_fused_frequency_loss_matches_float64_mirror_at_step_sizes for every shipped scale count, scales 1 / 2^i, i < n:
+    levels down to 1/16 with floored sizes (1200x680 -> 75x42) and non-trivial bilinear weights, same bars."""
+    from segs_slam_amd.frequency_loss import FusedFrequencyLoss
+    dev = torch.device("cuda:0")
+    H, W = size
+    img, gt = _images(H, W, dev, 11 + H + nscales)
+    lam = 0.01
+    scales = tuple(1.0 / 2 ** i for i in range(nscales))
+    fl = FusedFrequencyLoss(H, W, dev, lambda_high=lam, scales=scales, torch_fft=torch_fft)
+    assert fl.sizes[-1] == (H >> (nscales - 1), W >> (nscales - 1))
+    assert fl.folded == (nscales == 3 and not torch_fft and H % 4 == 0 and W % 4 == 0)
+    if fl.folded:
+        # the plan's own transforms store the half spectrum in whole tiles of 8 columns; the vendor library's do not
+        own = _own_transform_size(W // 2) and _own_transform_size(H)
+        assert own == ((H, W) != (480, 752))
+        wc = (W // 2 + 1 + 7) // 8 * 8 if own else W // 2 + 1
+        assert fl._target_floats == 3 * H * wc + 3 * (H // 2) * (W // 2) + 3 * (H // 4) * (W // 4)
+    base = torch.randn(3, H, W, device=dev) * 1e-9
+    for _ in range(2):
+        dL = base.clone()
+        loss_word = torch.full((1,), 0.5, device=dev)
+        val = float(fl(img, gt, dL, loss_word))
+    torch.cuda.synchronize()
+    assert abs(float(loss_word) - 0.5 - val) <= 1e-6 + 1e-5 * val
+    ties, taken = _check_against_float64(img, gt, lam, scales, val, dL - base)
+    print(f"{W}x{H} scales={nscales} torch_fft={torch_fft}: {ties} near ties, {taken} took the device's sign")
+
+
+def _evaluate(fl, img, gt):
+    dL = torch.zeros_like(img)
+    val = fl(img, gt, dL).clone()
+    torch.cuda.synchronize()
+    return val, dL
+
+
+@pytest.mark.parametrize("order", ["large_first", "small_first"])
+def test_several_plans_alive_in_one_process(order):
+    """One plan per image size, several alive at once (include/segs_train.h): creating a plan for a smaller image must not
+    break one made before it.  The folded plans launch the process-global transform kernels of csrc/real_fft.h with up to
+    ~92 KB of dynamic LDS (1200x680's column pass), a per-kernel attribute that a later, smaller plan must not lower.
+    Re-evaluating a plan after the others were made and run must give its first result bit for bit: every step of both paths
+    sums in a fixed order (one workgroup folds the partials), so the same inputs give the same bits."""
+    from segs_slam_amd.frequency_loss import FusedFrequencyLoss
+    dev = torch.device("cuda:0")
+    sizes = [(680, 1200), (240, 320), (170, 300)]           # folded + own transforms, folded + own transforms (small), per-scale
+    if order == "small_first":
+        sizes = [(240, 320), (680, 1200), (170, 300)]
+    inputs = [_images(H, W, dev, 21 + H) for H, W in sizes]
+    plans = []
+    first = None
+    for (H, W), (img, gt) in zip(sizes, inputs):
+        fl = FusedFrequencyLoss(H, W, dev, lambda_high=0.01)
+        assert fl.folded == (H % 4 == 0 and W % 4 == 0)
+        plans.append(fl)
+        val, dL = _evaluate(fl, img, gt)
+        assert float(val) > 0 and bool(dL.abs().max() > 0)
+        if first is None:
+            first = (val, dL)
+    img, gt = inputs[0]
+    for target in (gt, gt.clone()):                         # cached |FFT| table, and one made again by segs_freq_target
+        val, dL = _evaluate(plans[0], img, target)
+        assert torch.equal(val, first[0]), (float(val), float(first[0]))
+        assert torch.equal(dL, first[1]), float((dL - first[1]).abs().max())
+
+
 def test_folded_and_per_scale_plans_agree():
     """The alias-folded evaluation (one transform pair) against the per-scale evaluation (three pairs) of the same plan API:
     two float32 routes to the same numbers -- value 1e-6, coefficient-implied gradient within the flips' budget."""
@@ -151,9 +240,21 @@ def test_target_spectrum_cache_follows_the_target_tensor():
     assert not d.any()
 
 
-def _step_pair(fused, iteration, dev):
+def _mapper_config(path):
+    """A shipped configuration: the package's committed table, else the test extract of every shipped file's values."""
+    import json
+    import os
+    from segs_slam_amd import mapper_config as mc
+    try:
+        return mc.load_committed_config(path)
+    except KeyError:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mapper_cfg_values.json")) as f:
+            return mc.mapper_config_from_values(json.load(f)[path], path)
+
+
+def _step_pair(fused, iteration, dev, cfg_path="cfg/gaussian_mapper/RGB-D/Replica/office0.yaml"):
     from segs_slam_amd import mapper_config as mc, neural_gaussians as ng, scenes
-    cfg = mc.load_committed_config("cfg/gaussian_mapper/RGB-D/Replica/office0.yaml")
+    cfg = _mapper_config(cfg_path)
     cam = scenes.make_camera(320, 240, 300.0, 300.0, np.eye(3, dtype=np.float32), np.zeros(3, dtype=np.float32))
     model = ng.synthetic_model(4000, cfg.model, cam, dev, seed=3)
     step = mc.make_mapper_step(cfg, model, cam.width, cam.height)
@@ -173,10 +274,14 @@ def test_replica_mapper_step_with_fused_frequency_regulariser_matches_the_mirror
     """One forward/backward of the step the Replica cfg describes (Mapper.use_frequency_regularization 1, 3 scales,
     lambda_high 0.01, window (5 000, 25 500)): loss and every parameter gradient of the fused path against the path that
     evaluates the regulariser with the reference's op chain + autograd."""
+    _check_step_pair(iteration, expect_on)
+
+
+def _check_step_pair(iteration, expect_on, cfg_path="cfg/gaussian_mapper/RGB-D/Replica/office0.yaml"):
     dev = torch.device("cuda:0")
     res = {}
     for fused in (True, False):
-        step, kf, gt = _step_pair(fused, iteration, dev)
+        step, kf, gt = _step_pair(fused, iteration, dev, cfg_path)
         assert step._freq_active() == (False, expect_on)
         step.iteration += 0
         loss = step._forward_backward(kf, gt)
@@ -190,8 +295,24 @@ def test_replica_mapper_step_with_fused_frequency_regulariser_matches_the_mirror
         assert scale > 0 and float((a - b).abs().max()) <= 2e-4 * scale, name
     if expect_on:
         # and the regulariser is really in there: without it the loss is smaller
-        step, kf, gt = _step_pair(True, 3_000, dev)
+        step, kf, gt = _step_pair(True, 3_000, dev, cfg_path)
         assert float(step._forward_backward(kf, gt)) < la - 1e-4
+    return sa
+
+
+@pytest.mark.parametrize("cfg_path,nscales", [("cfg/gaussian_mapper/Stereo/EuRoC/EuRoC2.yaml", 2),
+                                              ("cfg/gaussian_mapper/RGB-D/Replica/room0.yaml", 4),
+                                              ("cfg/gaussian_mapper/Monocular/Replica/office3.yaml", 5)])
+def test_mapper_step_with_fused_frequency_regulariser_at_every_shipped_scale_count(cfg_path, nscales):
+    """test_replica_mapper_step_with_fused_frequency_regulariser_matches_the_mirror (3 scales) for one shipped configuration per
+    other Mapper.scale_num, inside its regulariser window: loss and every parameter gradient of the fused (per-scale) path
+    against the reference's op chain + autograd, same bars."""
+    cfg = _mapper_config(cfg_path)
+    assert cfg.use_frequency_regularization and cfg.use_multi_resolution and cfg.scale_num == nscales
+    assert cfg.high_frequency_regularization_start < 10_000 < cfg.frequency_regulization_until
+    step = _check_step_pair(10_000, True, cfg_path)
+    (fl,) = step._freq_fused.values()
+    assert len(fl.sizes) == nscales and not fl.folded
 
 
 _LIBRARY_ARM = r"""
