@@ -47,16 +47,23 @@ class NeuralDims:
         return out
 
 
-def _mlp(p, name, x):
-    h = F.relu(F.linear(x, p[name + ".0.weight"], p[name + ".0.bias"]))
-    return F.linear(h, p[name + ".2.weight"], p[name + ".2.bias"])
+def _mlp(p, name, x, relu_inputs=None):
+    pre = F.linear(x, p[name + ".0.weight"], p[name + ".0.bias"])
+    if relu_inputs is not None:
+        relu_inputs.append(pre)
+    return F.linear(F.relu(pre), p[name + ".2.weight"], p[name + ".2.bias"])
 
 
 def generate_neural_gaussians(dims: NeuralDims, anchor, offset, anchor_feat, scaling_log, mlp, camera_center, pose7,
-                              visible_mask):
+                              visible_mask, mask=None, relu_inputs=None):
     """anchor (A,3), offset (A,n_offsets,3), anchor_feat (A,feat_dim), scaling_log (A,6) [get_scaling = exp,
     src/gaussian_model.cpp get_scaling], mlp: dict name -> tensor, camera_center (3,), pose7 = (t_xyz, q_wxyz) of the
     keyframe (gaussian_renderer.cpp:258-261), visible_mask (A,) bool.
+    mask (visible anchors * n_offsets,) bool, optional: selects the kept rows in place of neural_opacity > 0 (:279-280), so
+    that a caller can evaluate the reference on another implementation's mask where an opacity within rounding of 0 may
+    have either sign.  None: the reference's own mask.
+    relu_inputs: a list, optional, that receives the input of every ReLU, (visible anchors, feat_dim) per MLP: where one of
+    them is within rounding of 0 the derivative of the step may be taken on either side.
     Returns (xyz, color, opacity, scaling, rot, neural_opacity, mask) exactly as gaussian_renderer.cpp:333."""
     feat = anchor_feat[visible_mask]                                  # :228
     anc = anchor[visible_mask]                                        # :229
@@ -67,7 +74,7 @@ def generate_neural_gaussians(dims: NeuralDims, anchor, offset, anchor_feat, sca
     ob_view = ob_view / ob_dist                                       # :234
     if dims.use_feat_bank:                                            # :236-249
         cat_view = torch.cat([ob_view, ob_dist], dim=1)
-        bank_weight = torch.softmax(_mlp(mlp, "mlp_feature_bank", cat_view), dim=1).unsqueeze(1)
+        bank_weight = torch.softmax(_mlp(mlp, "mlp_feature_bank", cat_view, relu_inputs), dim=1).unsqueeze(1)
         f = feat.unsqueeze(-1)
         f = (f[:, ::4, :1].repeat(1, 4, 1) * bank_weight[:, :, :1]
              + f[:, ::2, :1].repeat(1, 2, 1) * bank_weight[:, :, 1:2]
@@ -79,15 +86,16 @@ def generate_neural_gaussians(dims: NeuralDims, anchor, offset, anchor_feat, sca
         ob_pose = pose7.reshape(1, 7).expand(cat_local_view.shape[0], -1)
         appearance_feat = F.linear(ob_pose, mlp["mlp_apperance.0.weight"], mlp["mlp_apperance.0.bias"])
     x = cat_local_view if dims.add_opacity_dist else cat_local_view_wodist
-    neural_opacity = torch.tanh(_mlp(mlp, "mlp_opacity", x)).reshape(-1, 1)   # :273-278
-    mask = (neural_opacity > 0.0).view(-1)                            # :279-280
+    neural_opacity = torch.tanh(_mlp(mlp, "mlp_opacity", x, relu_inputs)).reshape(-1, 1)   # :273-278
+    if mask is None:
+        mask = (neural_opacity > 0.0).view(-1)                        # :279-280
     opacity = neural_opacity[mask]                                    # :282
     x = cat_local_view if dims.add_color_dist else cat_local_view_wodist
     if dims.appearance_dim > 0:
         x = torch.cat([x, appearance_feat], dim=1)
-    color = torch.sigmoid(_mlp(mlp, "mlp_color", x)).reshape(anc.shape[0] * dims.n_offsets, 3)   # :285-299
+    color = torch.sigmoid(_mlp(mlp, "mlp_color", x, relu_inputs)).reshape(anc.shape[0] * dims.n_offsets, 3)   # :285-299
     x = cat_local_view if dims.add_cov_dist else cat_local_view_wodist
-    scale_rot = _mlp(mlp, "mlp_cov", x).reshape(anc.shape[0] * dims.n_offsets, 7)                # :301-306
+    scale_rot = _mlp(mlp, "mlp_cov", x, relu_inputs).reshape(anc.shape[0] * dims.n_offsets, 7)   # :301-306
     offsets = grid_offsets.reshape(-1, 3)                             # :308
     concatenated = torch.cat([grid_scaling, anc], dim=-1)             # :309
     concatenated_repeated = concatenated.repeat(1, dims.n_offsets).view(anc.shape[0] * dims.n_offsets, -1)  # :315-316

@@ -129,6 +129,23 @@ def test_every_shipped_configuration_parses(tmp_path):
     assert cfg.use_frequency_regularization and cfg.scale_num == 3 and cfg.lambda_frequency_high == 0.01
 
 
+def test_every_shipped_model_shape_is_under_the_neural_parity_tests():
+    """The model shape of every shipped configuration -- appearance width, feature bank, the three add_*_dist inputs; a file
+    without a Model block reads as (0, no bank) -- is one that tests/test_neural_gpu.py compares with the float64 restatement,
+    both at the small sizes (CASES) and at a mapper-sized anchor count (COUNT_PARAMS).  A newly shipped shape fails here."""
+    from tests import test_neural_gpu as tn
+    with open(SHIPPED) as f:
+        shipped = json.load(f)
+    shapes = {}
+    for rel, values in sorted(shipped.items()):
+        shapes.setdefault(tn.model_shape(mc.mapper_config_from_values(values, rel).model), []).append(rel)
+    small = {tn.model_shape(kw) for kw in tn.CASES}
+    at_size = {tn.model_shape(tn.CASES[c]) for c, n in tn.COUNT_PARAMS if n >= 100_000}
+    assert len(shapes) >= 5
+    for shape, rels in shapes.items():
+        assert shape in small and shape in at_size, (shape, rels)
+
+
 @pytest.mark.gpu
 def test_mapper_step_from_configuration_applies_the_row_mask(tmp_path):
     from segs_slam_amd import neural_gaussians as ng, scenes
