@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -65,10 +65,14 @@ def _extend(st: DensifyState, new: Dict[str, torch.Tensor]):
             st.exp_avg_sq[g] = torch.cat([st.exp_avg_sq[g], torch.zeros_like(new[g])], dim=0)
 
 
-def anchor_growing(st: DensifyState, grads, threshold: float, offset_mask, rands: List[torch.Tensor]):
-    """:1559-1699.  rands[i] stands for torch::rand_like at level i (shape of `grads`)."""
+def anchor_growing(st: DensifyState, grads, threshold: float, offset_mask, rands: List[torch.Tensor],
+                   trace: Optional[List[Dict[str, int]]] = None):
+    """:1559-1699.  rands[i] stands for torch::rand_like at level i (shape of `grads`).  `trace`: when a list, one dict per
+    level that ran is appended -- candidates (slots that passed the tests), unique (their distinct voxels), in_grown (distinct
+    voxels already holding an anchor appended by an earlier level of this call), new (anchors appended)."""
     no = st.n_offsets
     init_length = st.params["anchor"].shape[0] * no
+    A_init = st.params["anchor"].shape[0]
     for i in range(st.update_depth):
         cur_threshold = threshold * (math.floor(st.update_hierachy_factor / 2) ** i)
         candidate_mask = (grads >= cur_threshold) & offset_mask
@@ -95,10 +99,15 @@ def anchor_growing(st: DensifyState, grads, threshold: float, offset_mask, rands
             gkey = grid_coords.to(torch.int64)
             pack = lambda t: ((t[:, 0] + (1 << 20)) << 42) | ((t[:, 1] + (1 << 20)) << 21) | (t[:, 2] + (1 << 20))  # noqa: E731
             remove_duplicates = torch.isin(pack(ukey), pack(gkey))
+            in_grown = int(torch.isin(pack(ukey), pack(gkey[A_init:])).sum())
         else:
             remove_duplicates = torch.zeros(0, dtype=torch.bool)
+            in_grown = 0
         remove_duplicates = ~remove_duplicates
         candidate_anchor = uniq[remove_duplicates] * cur_size
+        if trace is not None:
+            trace.append(dict(level=i, candidates=int(candidate_mask.sum()), unique=int(uniq.shape[0]), in_grown=in_grown,
+                              new=int(candidate_anchor.shape[0])))
         if candidate_anchor.shape[0] > 0:
             n_new = candidate_anchor.shape[0]
             new_scaling = torch.log(torch.ones_like(candidate_anchor).repeat(1, 2).float() * cur_size)
@@ -130,14 +139,14 @@ def prune_anchor(st: DensifyState, mask):
 
 
 def adjust_anchor(st: DensifyState, check_interval: int, success_threshold: float, grad_threshold: float, min_opacity: float,
-                  rands: List[torch.Tensor]):
-    """:1701-1762."""
+                  rands: List[torch.Tensor], trace: Optional[List[Dict[str, int]]] = None):
+    """:1701-1762.  `trace`: see anchor_growing."""
     no = st.n_offsets
     grads = st.offset_gradient_accum / st.offset_denom
     grads[grads.isnan()] = 0.0
     grads_norm = torch.linalg.norm(grads, dim=-1)
     offset_mask = (st.offset_denom > check_interval * success_threshold * 0.5).squeeze(1)
-    anchor_growing(st, grads_norm, grad_threshold, offset_mask, rands)
+    anchor_growing(st, grads_norm, grad_threshold, offset_mask, rands, trace)
     st.offset_denom[offset_mask] = 0
     A = st.params["anchor"].shape[0]
     st.offset_denom = torch.cat([st.offset_denom, torch.zeros(A * no - st.offset_denom.shape[0], 1)], dim=0)

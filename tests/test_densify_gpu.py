@@ -3,6 +3,10 @@ torch restatement of src/gaussian_model.cpp:1459-1762 (oracle/densify_ref.py).
 
 Integer / index work (which voxels receive an anchor, their order, the per-voxel feature maximum, row compaction) is
 compared exactly; the accumulated gradient norms to 1e-6 relative (sqrt rounding)."""
+import json
+import math
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -12,6 +16,48 @@ pytestmark = pytest.mark.gpu
 from oracle import densify_ref, neural_ref  # noqa: E402
 
 DIMS = dict(feat_dim=32, n_offsets=10, appearance_dim=0, use_feat_bank=False)
+NO = DIMS["n_offsets"]
+
+# ---- the densification settings of every shipped Scaffold configuration (the files that set Model.voxel_size)
+SHIPPED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mapper_cfg_values.json")
+TUPLE_FIELDS = ("voxel_size", "update_depth", "update_init_factor", "update_hierachy_factor", "densify_grad_threshold",
+                "success_threshold", "min_opacity", "update_interval")
+
+
+def densify_tuple(params):
+    """The DensifyParams fields adjust_anchor depends on, in TUPLE_FIELDS order."""
+    return tuple(getattr(params, k) for k in TUPLE_FIELDS)
+
+
+def shipped_densify_tuples():
+    """{tuple: [configuration files]} over the committed extract of the shipped configurations, read through mapper_config."""
+    from segs_slam_amd import mapper_config as mc
+    with open(SHIPPED) as f:
+        shipped = json.load(f)
+    out = {}
+    for rel, values in sorted(shipped.items()):
+        if "Model.voxel_size" in values:
+            out.setdefault(densify_tuple(mc.mapper_config_from_values(values, rel).densify), []).append(rel)
+    return out
+
+
+def _adjust_cases():
+    """Every shipped tuple at 40 anchors and at 2 500 anchors with the capacity one row above A (the storage grows inside
+    the call); then a map-sized case per tuple: 300 000 anchors for hierarchy factor 1 (thresholds 0 at levels 1-2, more than
+    2^20 candidates at one level), 60 001 and 300 000 (capacity A + 1) in turn for the others."""
+    cases, big = [], [(60_001, None), (300_000, 300_001)]
+    k = 0
+    for t in sorted(shipped_densify_tuples()):
+        cases += [(t, 40, None), (t, 2_500, 2_501)]
+        if t[3] == 1:
+            cases.append((t, 300_000, None))
+        else:
+            cases.append((t, *big[k % 2]))
+            k += 1
+    return cases
+
+
+ADJUST_CASES = _adjust_cases()
 
 
 def _model(A, seed, dev, capacity=None):
@@ -30,10 +76,19 @@ def _model(A, seed, dev, capacity=None):
 
 
 def test_training_statis_matches_restatement():
+    _check_training_statis(900, 3)
+
+
+def test_training_statis_at_map_scale():
+    """300 000 anchors (3 M candidate slots, 12 000 workgroups of 25 anchors), about 60 % of them visible."""
+    _check_training_statis(300_000, 13)
+
+
+def _check_training_statis(A, seed):
     from segs_slam_amd import densify, neural_gaussians as ng
     dev = torch.device("cuda:0")
-    A, no = 900, 10
-    model, _, g = _model(A, 3, dev)
+    no = 10
+    model, _, g = _model(A, seed, dev)
     dens = densify.AnchorDensifier(model)
     gen = ng.NeuralGaussians(model)
     visible = torch.rand(A, generator=g) < 0.6
@@ -101,9 +156,14 @@ def test_adjust_anchor_matches_restatement(A, seed, capacity):
 
     prune = dens.adjust_anchor(100, 0.8, 0.0002, 0.005, rands=[r.to(dev) for r in rands])
     torch.cuda.synchronize()
-    A1 = ref.params["anchor"].shape[0]
     grown = ref_prune.shape[0] - A
     assert grown > 0 and int(ref_prune.sum()) > 0, "the case must exercise both growing and pruning"
+    _assert_same_map(model, dens, prune, ref, ref_prune)
+
+
+def _assert_same_map(model, dens, prune, ref, ref_prune):
+    """Every output of adjust_anchor equal to the restatement's: integer and row outputs exactly, scaling to 1e-6."""
+    A1 = ref.params["anchor"].shape[0]
     assert model.A == A1
     np.testing.assert_array_equal(prune.cpu().numpy(), ref_prune.numpy())
     eq = lambda a, b, msg: np.testing.assert_array_equal(a.cpu().numpy(), b.numpy(), err_msg=msg)  # noqa: E731
@@ -118,6 +178,187 @@ def test_adjust_anchor_matches_restatement(A, seed, capacity):
         eq(model._view(model.exp_avg_sq, n), ref.exp_avg_sq[n], "exp_avg_sq " + n)
     for k in ("opacity_accum", "anchor_demon", "offset_gradient_accum", "offset_denom"):
         eq(dens.stat(k), getattr(ref, k), k)
+
+
+def _densifier_with_state(model, t, denom, accum, demon, opac, g):
+    """An AnchorDensifier of `model` at the settings of tuple `t`, its statistics set to the given values and the Adam
+    moments of every anchor row random; returns it with the restatement's DensifyState of the same map."""
+    from segs_slam_amd import densify
+    dev = model.device
+    A = model.A
+    anchor, offset, feat, scaling_log = (model.param(n).cpu() for n in ("anchor", "offset", "anchor_feat", "scaling"))
+    kw = dict(zip(TUPLE_FIELDS, t))
+    dens = densify.AnchorDensifier(model, densify.DensifyParams(**kw))
+    for k, v in (("offset_denom", denom), ("offset_gradient_accum", accum), ("anchor_demon", demon), ("opacity_accum", opac)):
+        dens._stats[k][:v.numel()] = v.to(dev)
+    m_rand = {n: torch.randn(A, w, generator=g) for n, w in model.widths.items()}
+    v_rand = {n: torch.rand(A, w, generator=g) for n, w in model.widths.items()}
+    for n in model.widths:
+        model._view(model.exp_avg, n).copy_(m_rand[n].view(model._view(model.exp_avg, n).shape))
+        model._view(model.exp_avg_sq, n).copy_(v_rand[n].view(model._view(model.exp_avg_sq, n).shape))
+    rot = torch.zeros(A, 4)
+    rot[:, 0] = 1.0
+    moments = lambda d: {"anchor": d["anchor"], "offset": d["offset"].view(A, NO, 3), "anchor_feat": d["anchor_feat"],  # noqa: E731
+                         "scaling": d["scaling"]}
+    ref = densify_ref.DensifyState(
+        params={"anchor": anchor, "offset": offset, "anchor_feat": feat, "opacity": torch.zeros(A, 1), "scaling": scaling_log,
+                "rotation": rot},
+        exp_avg=moments(m_rand), exp_avg_sq=moments(v_rand), opacity_accum=opac.view(-1, 1).clone(),
+        anchor_demon=demon.view(-1, 1).clone(), offset_gradient_accum=accum.view(-1, 1).clone(),
+        offset_denom=denom.view(-1, 1).clone(), voxel_size=kw["voxel_size"], update_depth=kw["update_depth"],
+        update_init_factor=kw["update_init_factor"], update_hierachy_factor=kw["update_hierachy_factor"])
+    return dens, ref
+
+
+def _level_sizes(t):
+    """cur_size of every growing level, as anchor_growing forms it (a float32 value)."""
+    vs, depth, init, hier = t[:4]
+    return [float(torch.tensor(vs * math.floor(init / hier ** i), dtype=torch.float32)) for i in range(depth)]
+
+
+# ---- tie policy of the map-scale cases.  The device forms xyz = anchor + offset * expf(scaling) and rintf(xyz / cur_size),
+# the restatement the same float32 operations with CPU torch.exp; the two exp implementations may differ by 1 ulp.
+#  * Directly that moves xyz by |offset * exp(s)| * 2^-23 at most: <= 0.12 m * 1.19e-7 = 1.4e-8 m for the N(0,1) offsets and
+#    exp(s) <= 0.03 used here (6e-9 m for the 5-cm cluster slots), i.e. <= 1.4e-5 voxel at 1 mm -- TIE_MARGIN = 1e-4 voxel
+#    is 7x that for the largest offsets and 16x for the cluster slots.  A slot whose float64 xyz / cur_size lies within
+#    TIE_MARGIN of a half-integer at any level is redrawn.
+#  * But when the float32 sum anchor + offset * exp(s) then rounds to the neighbouring float, xyz moves by 1 ulp of xyz:
+#    2.4e-7 m for |xyz| < 4 m, 2.4e-4 voxel at 1 mm, more than the margin.  So a slot is also redrawn when its voxel changes
+#    at some level with exp(s) moved 1 ulp either way in the float32 formula.  Any two exp implementations that are each
+#    within 1 ulp of the true value return one of the two floats around it, so this covers every such pair exactly.
+TIE_MARGIN = 1e-4
+
+
+def _redraw_ties(anchor, offset, scaling_log, sizes, g):
+    """Redraws (in place) the offsets of the slots the tie policy above excludes; returns (slots flagged at the first pass,
+    redraws in all)."""
+    a32 = anchor.unsqueeze(1)
+    e = torch.exp(scaling_log)[:, :3].unsqueeze(1)                     # the restatement's float32 exp, same call
+    e_ulp = (torch.nextafter(e, torch.zeros_like(e)), torch.nextafter(e, torch.full_like(e, math.inf)))
+    e64 = torch.exp(scaling_log.double())[:, :3].unsqueeze(1)
+    first, total = None, 0
+    while True:
+        q64 = anchor.double().unsqueeze(1) + offset.double() * e64
+        bad = torch.zeros(offset.shape[:2], dtype=torch.bool)
+        for cs in sorted(set(sizes)):
+            q = q64 / cs
+            bad |= ((q - torch.floor(q) - 0.5).abs() < TIE_MARGIN).any(-1)
+            v = torch.round((a32 + offset * e) / cs)
+            for e2 in e_ulp:
+                bad |= (torch.round((a32 + offset * e2) / cs) != v).any(-1)
+        n = int(bad.sum())
+        first = n if first is None else first
+        if n == 0:
+            return first, total
+        total += n
+        offset[bad] = torch.randn(n, 3, generator=g)
+
+
+BOX_LO, BOX_EXT = torch.tensor([-3.0, -2.0, -1.5]), torch.tensor([6.0, 4.0, 3.0])      # a Replica-sized room around the origin
+
+
+def _map_scene(A, t, seed):
+    """Anchors in a 6 x 4 x 3 m room, log-scales near the 1-mm grid, N(0,1) offsets; every 7th anchor's offsets tiny
+    (candidates in the parent's own voxel); the last ~10 % of the anchors in clusters of 12 parents within 2 mm whose slot k
+    all point at one spot 5 cm away (long runs of candidates of many parents in one voxel: the per-voxel feature maximum);
+    statistics scaled to the tuple so that every level grows and pruning happens, 5 % of the gradients exactly 0."""
+    g = torch.Generator().manual_seed(seed)
+    anchor = torch.rand(A, 3, generator=g) * BOX_EXT + BOX_LO
+    scaling_log = torch.log(0.002 + 0.028 * torch.rand(A, 6, generator=g))
+    offset = torch.randn(A, NO, 3, generator=g)
+    offset[::7] *= 1e-3
+    n_cl = max(1, A // 120)
+    first = A - 12 * n_cl
+    centre = anchor[first::12][:n_cl]
+    member = centre.repeat_interleave(12, 0) + (torch.rand(12 * n_cl, 3, generator=g) - 0.5) * 0.004
+    anchor[first:] = member
+    target = centre.unsqueeze(1) + 0.05 * torch.nn.functional.normalize(torch.randn(n_cl, NO, 3, generator=g), dim=-1)
+    offset[first:] = (target.repeat_interleave(12, 0) - member.unsqueeze(1)) / torch.exp(scaling_log[first:, :3]).unsqueeze(1)
+    first_pass, redraws = _redraw_ties(anchor, offset, scaling_log, _level_sizes(t), g)
+    feat = torch.randn(A, 32, generator=g)
+    interval, thr, min_op = t[7], t[4], t[6]
+    denom = torch.floor(torch.rand(A * NO, generator=g) * interval)     # offset_mask (> 0.4 interval): ~60 % of the slots
+    accum = torch.rand(A * NO, generator=g) * denom * (8 * thr)          # gradient ~ U(0, 8 thr): every level's threshold cuts
+    accum[torch.rand(A * NO, generator=g) < 0.05] = 0.0
+    demon = torch.floor(torch.rand(A, generator=g) * 2 * interval)      # judged (> 0.8 interval): ~60 % of the anchors
+    opac = torch.rand(A, generator=g) * demon * 2 * min_op              # half of the judged ones pruned
+    rands = [torch.rand(A * NO, generator=g) for _ in range(t[1])]
+    return (anchor, offset, feat, scaling_log), (denom, accum, demon, opac), rands, (first_pass, redraws), g
+
+
+@pytest.mark.parametrize("t,A,capacity", ADJUST_CASES, ids=[f"hier{t[3]}-thr{t[4]}-every{t[7]}-A{A}" for t, A, _ in ADJUST_CASES])
+def test_adjust_anchor_at_shipped_settings(t, A, capacity):
+    """adjust_anchor at every shipped densification tuple, up to map size: growth at 1/4/16-mm voxels in a room-sized map,
+    pruning, storage growth, and -- at 300 000 anchors with hierarchy factor 1 -- more than 2^20 candidates at one level
+    (scan_sums_kernel past its first round, 63-bit keys sorted in the millions).  Exact parity under the tie policy above."""
+    from segs_slam_amd import neural_gaussians as ng
+    dev = torch.device("cuda:0")
+    seed = 1000 + A % 977 + 10 * t[3] + int(1e5 * t[4]) + t[7]
+    (anchor, offset, feat, scaling_log), (denom, accum, demon, opac), rands, (first_pass, redraws), g = _map_scene(A, t, seed)
+    assert first_pass < 0.005 * A * NO, f"the tie policy redrew {first_pass} of {A * NO} slots"
+    _, _, _, _, mlp = neural_ref.random_model(neural_ref.NeuralDims(**DIMS), 1, seed)
+    model = ng.ScaffoldModel(A, ng.ModelDims(**DIMS), dev, capacity=capacity)
+    model.load(anchor, offset, feat, scaling_log, mlp)
+    dens, ref = _densifier_with_state(model, t, denom, accum, demon, opac, g)
+    interval, success, thr, min_op = t[7], t[5], t[4], t[6]
+    trace = []
+    ref_prune = densify_ref.adjust_anchor(ref, interval, success, thr, min_op, rands, trace=trace)
+    prune = dens.adjust_anchor(interval, success, thr, min_op, rands=[r.to(dev) for r in rands])
+    torch.cuda.synchronize()
+    info = f"tie-redrawn slots {first_pass} (redraws {redraws}) of {A * NO}; levels {trace}"
+    assert len(trace) == t[1] and all(lv["new"] > 0 for lv in trace) and int(ref_prune.sum()) > 0, info
+    if capacity is not None:
+        assert model.capacity > capacity, info                     # the storage grew inside the call
+    if A >= 2_500:
+        assert sum(lv["in_grown"] for lv in trace) > 0, info       # candidates in voxels an earlier level of this call filled
+    if t[3] == 1:
+        grads = (accum / denom).nan_to_num(0.0)
+        zero_in = (grads == 0) & (denom > interval * success * 0.5) & (rands[1] > 0.25)
+        assert int(zero_in.sum()) > 0, info                         # threshold 0 at level 1 admits gradient-0 slots (>=)
+        if A == 300_000:
+            assert max(lv["candidates"] for lv in trace) > 1 << 20, info
+    _assert_same_map(model, dens, prune, ref, ref_prune)
+
+
+def test_adjust_anchor_rounds_exact_half_voxels_to_even():
+    """Candidates exactly on half-integer voxel coordinates, on both sides of zero: voxel_size = 2^-10 makes every cur_size a
+    power of two and scaling_log = 0 makes exp exactly 1, so xyz / cur_size is exact on both sides.  The device's rintf and
+    the restatement's torch.round both round half to even; round-half-away (roundf) places other voxels."""
+    from segs_slam_amd import neural_gaussians as ng
+    dev = torch.device("cuda:0")
+    t = (2.0 ** -10, 3, 16, 4, 1e-3, 0.8, 0.005, 100)
+    A = 32
+    g = torch.Generator().manual_seed(77)
+    anchor = torch.zeros(A, 3)
+    anchor[:, 0] = 1.0 + torch.arange(A) / 16.0                   # parents on the grid, far from the candidates
+    anchor[:, 1:] = 1.0
+    level = torch.arange(A * NO) % 2                               # half of the slots tie at level 0 (2^-6), half at level 2
+    cs = torch.where(level == 0, 2.0 ** -6, 2.0 ** -10).unsqueeze(1)
+    k = torch.randint(-6, 6, (A * NO, 3), generator=g).float()
+    target = (k + 0.5) * cs                                        # exact half-integers of that level's voxel
+    offset = (target - anchor.repeat_interleave(NO, 0)).view(A, NO, 3)
+    assert torch.equal(anchor.repeat_interleave(NO, 0) + offset.view(-1, 3), target)
+    scaling_log = torch.zeros(A, 6)
+    feat = torch.randn(A, 32, generator=g)
+    _, _, _, _, mlp = neural_ref.random_model(neural_ref.NeuralDims(**DIMS), 1, 77)
+    model = ng.ScaffoldModel(A, ng.ModelDims(**DIMS), dev)
+    model.load(anchor, offset, feat, scaling_log, mlp)
+    denom = torch.full((A * NO,), 100.0)
+    accum = torch.full((A * NO,), 100.0)                            # gradient 1 >= 4 thr: a candidate at every level
+    dens, ref = _densifier_with_state(model, t, denom, accum, torch.zeros(A), torch.zeros(A), g)
+    rands = [torch.full((A * NO,), 0.99) for _ in range(3)]
+    trace = []
+    ref_prune = densify_ref.adjust_anchor(ref, 100, 0.8, 1e-3, 0.005, rands, trace=trace)
+    prune = dens.adjust_anchor(100, 0.8, 1e-3, 0.005, rands=[r.to(dev) for r in rands])
+    torch.cuda.synchronize()
+    # the restatement's first level is round-half-to-even, and round-half-away would differ from it
+    q = (target / 2.0 ** -6).numpy()
+    even = np.unique(np.rint(q) + 0.0, axis=0)
+    away = np.unique(np.trunc(q + np.copysign(0.5, q)) + 0.0, axis=0)
+    n0 = trace[0]["new"]
+    assert n0 == even.shape[0] and not np.array_equal(even, away)
+    np.testing.assert_array_equal(ref.params["anchor"][A:A + n0].numpy(), (even * 2.0 ** -6).astype(np.float32))
+    _assert_same_map(model, dens, prune, ref, ref_prune)
 
 
 def test_trainer_keeps_running_through_densification():
@@ -224,6 +465,42 @@ def test_create_from_pcd_and_increase_pcd_match_restatement():
     gt = torch.full((3, cam.height, cam.width), 0.5, device=dev)
     losses = [float(step.training_once([kf], [gt])) for _ in range(30)]
     assert np.isfinite(losses).all() and losses[-1] < losses[0]
+
+
+def test_create_from_pcd_and_increase_pcd_at_millimetre_voxels():
+    """createFromPcd / increasePcd at the shipped voxel_size = 0.001 on dense depth surfaces: more than 65 536 anchors, so
+    simple-knn runs past its first round of 256 candidate boxes; the same assertions as at 5-cm voxels."""
+    from segs_slam_amd import densify, neural_gaussians as ng
+    from tests.test_points import depth_surface_points, knn_oracle
+    dev = torch.device("cuda:0")
+    vs = 0.001
+
+    def restate(p):
+        u = (torch.unique(torch.round(p / vs), dim=0, sorted=True) * vs).to(torch.float32)
+        d2 = torch.from_numpy(knn_oracle(u.numpy())).clamp_min(0.0000001)
+        return u, torch.log(torch.sqrt(d2)).unsqueeze(1).repeat(1, 6)
+
+    def off_ties(p):
+        # torch divides a GPU tensor by a scalar as a multiplication by its reciprocal, the CPU divides: the quotients may
+        # differ by an ulp (6e-5 voxel at 0.6 m), so points within 1e-3 voxel of a half-integer are left out
+        q = p.double() / vs
+        return p[((q - torch.floor(q) - 0.5).abs() > 1e-3).all(1)]
+
+    pts = off_ties(torch.from_numpy(depth_surface_points(480, 360, 700.0, 31)))
+    model = ng.create_from_pcd(pts, ng.ModelDims(), vs, dev)
+    u, sc = restate(pts)
+    A = u.shape[0]
+    assert model.A == A and 65_536 < A < pts.shape[0]
+    assert torch.equal(model.param("anchor").cpu(), u)
+    assert torch.allclose(model.param("scaling").cpu(), sc, rtol=1e-6, atol=1e-6)
+    dens = densify.AnchorDensifier(model, densify.DensifyParams(voxel_size=vs))
+    new = torch.from_numpy(depth_surface_points(320, 240, 500.0, 32)) + torch.tensor([0.05, -0.02, 0.3])
+    new = off_ties(torch.cat([new, pts[:5000]]))                # some fall into voxels that already hold an anchor: kept
+    n_new = dens.increase_pcd(new.to(dev))
+    u2, sc2 = restate(new)
+    assert n_new == u2.shape[0] and model.A == A + n_new
+    assert torch.equal(model.param("anchor")[A:].cpu(), u2) and torch.equal(model.param("anchor")[:A].cpu(), u)
+    assert torch.allclose(model.param("scaling")[A:].cpu(), sc2, rtol=1e-6, atol=1e-6)
 
 
 def test_coarse_anchor_set_is_created_and_grown_like_the_reference():

@@ -146,6 +146,33 @@ def test_every_shipped_model_shape_is_under_the_neural_parity_tests():
         assert shape in small and shape in at_size, (shape, rels)
 
 
+def test_every_shipped_densification_tuple_is_under_the_adjust_anchor_parity_tests():
+    """The densification settings of every shipped Scaffold configuration -- (voxel_size, update_depth, update_init_factor,
+    update_hierachy_factor, densify_grad_threshold, success_threshold, min_opacity, update_interval) -- are a case of
+    tests/test_densify_gpu.py::test_adjust_anchor_at_shipped_settings, at the small sizes and at a map size; the map-sized
+    cases include 300 000 anchors at hierarchy factor 1 and an anchor count that is not a multiple of 25.  A newly shipped
+    tuple, or a case list that lost one, fails here."""
+    from tests import test_densify_gpu as td
+    with open(SHIPPED) as f:
+        shipped = json.load(f)
+    tuples = {}
+    for rel, values in sorted(shipped.items()):
+        if "Model.voxel_size" in values:
+            tuples.setdefault(td.densify_tuple(mc.mapper_config_from_values(values, rel).densify), []).append(rel)
+    assert sum(len(r) for r in tuples.values()) == 30 and len(tuples) >= 4
+    assert any(t[3] == 1 for t in tuples)                         # cfg/gaussian_mapper/RGB-D/ScanNet/scannet_rgbd.yaml
+    sizes = {}
+    for t, A, _ in td.ADJUST_CASES:
+        sizes.setdefault(t, set()).add(A)
+    for t, rels in tuples.items():
+        assert t in sizes and {40, 2_500} <= sizes[t] and max(sizes[t]) >= 60_001, (t, rels)
+        if t[3] == 1:
+            assert 300_000 in sizes[t], (t, rels)
+    all_sizes = set().union(*sizes.values())
+    assert {40, 2_500, 60_001, 300_000} <= all_sizes and any(A % 25 for A in all_sizes)
+    assert any(cap is not None and cap == A + 1 for _, A, cap in td.ADJUST_CASES)
+
+
 @pytest.mark.gpu
 def test_mapper_step_from_configuration_applies_the_row_mask(tmp_path):
     from segs_slam_amd import neural_gaussians as ng, scenes

@@ -355,18 +355,34 @@ def test_preprocess_backward_clamped_jacobian_and_precomputed_covariance_branche
         assert np.all(err <= 1e-5 * np.abs(want) + 1e-5 * np.abs(want).max()), (k, float(err.max()), float(np.abs(want).max()))
 
 
+def _voxel_keys(rng, n):
+    """63-bit keys packed like pack_key in csrc/densify.hip: three 21-bit voxel coordinates biased by 2^20, each with few
+    distinct values (1-mm voxels of a room around the origin, on a coarse lattice), so that runs of equal keys are long."""
+    bias = np.int64(1 << 20)
+    f = [(rng.integers(-3000, 3000, n) // 173 * 173 + bias).astype(np.uint64) for _ in range(3)]
+    return (f[0] << np.uint64(42)) | (f[1] << np.uint64(21)) | f[2]
+
+
 # sizes on both sides of the count kernel's chunk policy (1 / 2 / 4 tiles per chunk at <= 256 / <= 2048 / more sort tiles) and
-# grids that are not multiples of the 8 XCDs the scatter and count kernels deal their tiles to
+# grids that are not multiples of the 8 XCDs the scatter and count kernels deal their tiles to; the densifier's full-width
+# voxel keys (end_bit 63) at the candidate counts of a map-sized adjust_anchor, and all 64 bits with the top one set
 @pytest.mark.parametrize("n,end_bit", [(1, 44), (63, 40), (4096, 44), (4097, 45), (100_000, 44), (1_000_003, 48), (5000, 7),
-                                       (524_288, 44), (524_289, 33), (4_194_305, 36)])
+                                       (524_288, 44), (524_289, 33), (4_194_305, 36), (1_048_577, 63), (3_000_017, 63),
+                                       (1_500_001, 64)])
 def test_sort_pairs(n, end_bit):
     """Stable LSD radix sort on key bits [0,end_bit) == numpy stable argsort of the masked keys."""
     import ctypes as C
     from segs_slam_amd import _capi
     rng = np.random.default_rng(n)
-    # skewed keys: few distinct tile ids / exponent bytes, many ties
-    keys = (rng.integers(0, 3000, n, dtype=np.uint64) << np.uint64(32)) | \
-           (rng.integers(0x3E000000, 0x40C00000, n, dtype=np.uint64) & np.uint64(0xFFFFF000))
+    if end_bit >= 63:
+        keys = _voxel_keys(rng, n)
+        if end_bit == 64:
+            keys |= rng.integers(0, 2, n, dtype=np.uint64) << np.uint64(63)
+            assert (keys >> np.uint64(63)).any() and not (keys >> np.uint64(63)).all()
+    else:
+        # skewed keys: few distinct tile ids / exponent bytes, many ties
+        keys = (rng.integers(0, 3000, n, dtype=np.uint64) << np.uint64(32)) | \
+               (rng.integers(0x3E000000, 0x40C00000, n, dtype=np.uint64) & np.uint64(0xFFFFF000))
     vals = np.arange(n, dtype=np.uint32)
     mask = np.uint64((1 << end_bit) - 1)
     order = np.argsort(keys & mask, kind="stable")
