@@ -296,6 +296,56 @@ int segs_rasterize_backward_resident_depth(char* geom_buffer, char* binning_buff
                                            float* dL_dsh, float* dL_dscale, float* dL_drot, const segs_depth_grads* depth_grads,
                                            void* stream);
 
+/* ---- Gradients of the render with respect to the two camera matrices (no reference counterpart: the reference's backward
+ * stops at the Gaussians).  viewmatrix and projmatrix are taken as two INDEPENDENT inputs in their transposed layout; a caller
+ * whose projmatrix is viewmatrix x P chains the two results through that product itself.  Per binned Gaussian the backward's
+ * per-Gaussian stage adds, with dt the gradient of the view-space point (+ the depth map's dL/dz on its z),
+ *   dL/dview[12 + i] += dt_i,   dL/dview[4 j + i] += dt_i p_j + (J^T dL/d(J Wv))[i][j]      i, j < 3
+ *   dL/dproj[4 j + i] += dh_i p_j (p_3 = 1),   dh = (g.x w, g.y w, 0, -(g.x hom.x + g.y hom.y) w^2),  g = dL/dmean2D, w = 1/(hom.w + 1e-7)
+ * (a clamped view-space coordinate passes nothing, as everywhere else); dL/dview[4 j + 3] and dL/dproj[4 j + 2] are written as 0.
+ * The 24 sums are formed without atomics -- per workgroup on chip, then over the workgroups' rows in `temp` in a fixed order -- so
+ * given per-Gaussian inputs give the same bits every time.  `temp` holds segs_camera_grad_temp_bytes(rows) bytes, rows >= P
+ * (the resident form: geom_rows).  Every output of the entry point each one extends is still written, and a NULL struct pointer
+ * makes the call exactly that entry point.  With P == 0 or R == 0 both matrices are zero-filled.  The SH colour branch depends on
+ * campos, which these gradients do not cover: with `shs` the calls return SEGS_ERR_INVALID_ARGUMENT. */
+typedef struct segs_camera_grads {
+  float* dL_dviewmatrix;   /* 16 */
+  float* dL_dprojmatrix;   /* 16 */
+  char* temp;
+} segs_camera_grads;
+size_t segs_camera_grad_temp_bytes(int rows);
+/* extends segs_rasterize_backward_depth (+ camera_grads) */
+int segs_rasterize_backward_camera(int P, int D, int M, int R,
+                                   const float* background, int width, int height,
+                                   const float* means3D, const float* shs, const float* colors_precomp,
+                                   const float* scales, float scale_modifier, const float* rotations,
+                                   const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                   const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                   char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                   const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                   float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                   float* dL_dscale, float* dL_drot, const segs_depth_grads* depth_grads,
+                                   const segs_camera_grads* camera_grads, void* stream);
+/* extends segs_rasterize_backward_resident_depth (+ camera_grads): no host synchronisation, hipGraph-capturable, and the
+ * accumulator rows stay clean */
+int segs_rasterize_backward_resident_camera(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,
+                                            int geom_rows, int P, int D, int M, const float* background, int width, int height,
+                                            const float* means3D, const float* shs, const float* scales, float scale_modifier,
+                                            const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                            const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                            const int* radii, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                                            float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                                            float* dL_dsh, float* dL_dscale, float* dL_drot, const segs_depth_grads* depth_grads,
+                                            const segs_camera_grads* camera_grads, void* stream);
+/* extends segs_debug_preprocess_backward: the per-Gaussian stage alone, + an optional per-Gaussian dL/dz of the view-space depth
+ * (P floats, or NULL) + camera_grads */
+int segs_debug_preprocess_backward_camera(int P, int width, int height, const float* means3D, const int* radii,
+                                          const float* scales, float scale_modifier, const float* rotations,
+                                          const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                          float tan_fovx, float tan_fovy, const float* dL_dmean2D, const float* dL_dconic,
+                                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dscale, float* dL_drot,
+                                          const float* dL_dz, const segs_camera_grads* camera_grads, void* stream);
+
 /* ---- Measurement support (bench.py): per-kernel timing with HIP events recorded on the launch stream.
  * kernel_mask bit i selects kernel id i (ids 0..segs_profile_kernel_count()-1, names via
  * segs_profile_kernel_name).  segs_profile_end() synchronises the recorded events and accumulates;

@@ -40,6 +40,11 @@ class DepthGrads(C.Structure):
     _fields_ = [("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p)]
 
 
+class CameraGrads(C.Structure):
+    """segs_camera_grads (include/segs_raster.h)."""
+    _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("temp", C.c_void_p)]
+
+
 class AdamSegment(C.Structure):
     """segs_adam_segment (include/segs_train.h)."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_double)]
@@ -81,6 +86,11 @@ for _name in ("segs_rasterize_forward", "segs_rasterize_backward", "segs_rasteri
     _res, _args = SYMBOLS[_name]
     _at = len(_args) - (2 if _name == "segs_rasterize_forward" else 1)   # (segs_rasterize_forward ends with stream, num_rendered)
     SYMBOLS[_name + "_depth"] = (_res, _args[:_at] + [_vp] + _args[_at:])
+# the `_camera` backwards: the `_depth` backward plus one more struct pointer in front of `stream`
+for _name in ("segs_rasterize_backward", "segs_rasterize_backward_resident"):
+    _res, _args = SYMBOLS[_name + "_depth"]
+    SYMBOLS[_name + "_camera"] = (_res, _args[:-1] + [_vp] + _args[-1:])
+SYMBOLS["segs_camera_grad_temp_bytes"] = (_sz, [_i])
 SYMBOLS.update({
     "segs_visible_filter": (_i, [_i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp]),
     "segs_visible_filter_log_scales": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _vp, _vp]),
@@ -93,6 +103,8 @@ SYMBOLS.update({
     "segs_debug_unpack_image": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "segs_debug_preprocess_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp,
                                              _vp, _vp, _vp, _vp]),
+    "segs_debug_preprocess_backward_camera": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "segs_sort_pairs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "segs_knn_temp_bytes": (_sz, [_i]),
     "segs_knn_mean_dist2": (_i, [_i, _vp, _vp, _vp, _vp]),

@@ -327,6 +327,28 @@ int launch_render_fwd(uint32_t tiles, const uint2* ranges, const uint32_t* point
   return SEGS_OK;
 }
 
+// Camera form of the backward (segs_*_camera entry points): checks the struct, zero-fills both 4x4 gradients when there is nothing
+// to sum (*live = false: the caller then runs the form without it), and the fixed-order sum over the workgroups' partial rows.
+int camera_grads_begin(const segs_camera_grads* cam, const float* shs, bool empty, hipStream_t st, bool* live) {
+  *live = false;
+  if (!cam) return SEGS_OK;
+  if (!cam->dL_dviewmatrix || !cam->dL_dprojmatrix || !cam->temp) return fail(SEGS_ERR_INVALID_ARGUMENT, "segs_camera_grads: null field");
+  if (shs) return fail(SEGS_ERR_INVALID_ARGUMENT, "camera gradients need colors_precomp: the SH colours depend on campos, which they do not cover");
+  if (empty) {
+    HIP_TRY(hipMemsetAsync(cam->dL_dviewmatrix, 0, 16 * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(cam->dL_dprojmatrix, 0, 16 * sizeof(float), st));
+    return SEGS_OK;
+  }
+  *live = true;
+  return SEGS_OK;
+}
+float* camera_partials(const segs_camera_grads* cam) { return (float*)align_ptr(cam->temp); }
+int camera_grads_finish(const segs_camera_grads* cam, int nblocks, hipStream_t st) {
+  camera_grad_reduce_kernel<<<1, 960, 0, st>>>(camera_partials(cam), nblocks, cam->dL_dviewmatrix, cam->dL_dprojmatrix);
+  LAUNCH_TRY("camera_grad_reduce_kernel");
+  return SEGS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -476,10 +498,12 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
                             float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                             const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                            bool self_clean, int geom_rows, const segs_depth_grads* dgrad) {
+                            bool self_clean, int geom_rows, const segs_depth_grads* dgrad, const segs_camera_grads* cam) {
   hipStream_t st = (hipStream_t)stream;
   if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(SEGS_ERR_INVALID_ARGUMENT, "bad sizes");
   if (geom_rows < P) return fail(SEGS_ERR_INVALID_ARGUMENT, "geom_rows must be >= P");
+  bool cam_live = false;   // without Gaussians or instances both matrices are zero-filled here, ahead of the early return
+  if (int rc = camera_grads_begin(cam, shs, P == 0 || R == 0, st, &cam_live)) return rc;
   if (P == 0) return SEGS_OK;  // src/rasterize_points.cu:159
   if (shs && (!campos || !dL_dsh || M <= 0)) return fail(SEGS_ERR_INVALID_ARGUMENT, "SH path needs campos, dL_dsh and M > 0");
   if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dpix || !background || !means3D || !viewmatrix || !projmatrix)
@@ -525,12 +549,18 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
   }
   { PROF(K_PREPROCESS_BWD);
   // row dword [9] (dL/dz) is only ever non-zero after a depth-map gradient; every clear of a row covers it either way
-  (dL_ddepth ? preprocess_bwd_kernel<true> : preprocess_bwd_kernel<false>)<<<G.L.nblocks, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
+  // camera form: + one row of partial sums per workgroup, added up by a second kernel inside the same profile slot
+  auto* const kernel = cam_live ? (dL_ddepth ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<false, true>)
+                                : (dL_ddepth ? preprocess_bwd_kernel<true, false> : preprocess_bwd_kernel<false, false>);
+  kernel<<<G.L.nblocks, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
                                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x, focal_y,
                                                      tan_fovx, tan_fovy, G.gacc(), (float)width, (float)height, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                                                     dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, self_clean ? 1 : 0);
-  }
+                                                     dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, self_clean ? 1 : 0, nullptr,
+                                                     cam_live ? camera_partials(cam) : nullptr);
   LAUNCH_TRY("preprocess_bwd_kernel");
+  if (cam_live)
+    if (int rc = camera_grads_finish(cam, G.L.nblocks, st)) return rc;
+  }
   if (shs) {   // SH colour branch (off the live SEGS-SLAM path): its own pass over the summed dL/dcolor
     sh_backward_kernel<<<G.L.nblocks, 256, 0, st>>>(P, means3D, radii, shs, D, M, campos, G.clamped(), dL_dcolor, dL_dmean3D, dL_dsh);
     LAUNCH_TRY("sh_backward_kernel");
@@ -549,7 +579,7 @@ int segs_rasterize_backward(int P, int D, int M, int R, const float* background,
   return rasterize_backward_impl(P, D, M, R, background, width, height, means3D, shs, scales, scale_modifier, rotations,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
                                  image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                 dL_dscale, dL_drot, stream, false, P, nullptr);
+                                 dL_dscale, dL_drot, stream, false, P, nullptr, nullptr);
 }
 
 int segs_rasterize_backward_depth(int P, int D, int M, int R, const float* background, int width, int height,
@@ -564,7 +594,24 @@ int segs_rasterize_backward_depth(int P, int D, int M, int R, const float* backg
   return rasterize_backward_impl(P, D, M, R, background, width, height, means3D, shs, scales, scale_modifier, rotations,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
                                  image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                 dL_dscale, dL_drot, stream, false, P, depth_grads);
+                                 dL_dscale, dL_drot, stream, false, P, depth_grads, nullptr);
+}
+
+size_t segs_camera_grad_temp_bytes(int rows) { return align_up((size_t)((rows < 0 ? 0 : rows) + 255) / 256 * CAM_SUMS * sizeof(float)) + ALIGN; }
+
+int segs_rasterize_backward_camera(int P, int D, int M, int R, const float* background, int width, int height,
+                                   const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                                   float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                   const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                   float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                   const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                   float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                   const segs_depth_grads* depth_grads, const segs_camera_grads* camera_grads, void* stream) {
+  (void)colors_precomp;
+  return rasterize_backward_impl(P, D, M, R, background, width, height, means3D, shs, scales, scale_modifier, rotations,
+                                 cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+                                 image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                 dL_dscale, dL_drot, stream, false, P, depth_grads, camera_grads);
 }
 
 static int visible_filter_impl(int P, int width, int height, const float* means3D, const float* scales, int log_scale_stride,
@@ -687,13 +734,39 @@ int segs_debug_preprocess_backward(int P, int width, int height, const float* me
   if (!means3D || !radii || !viewmatrix || !projmatrix || !dL_dmean2D || !dL_dconic || !dL_dmean3D || !dL_dcov3D)
     return fail(SEGS_ERR_INVALID_ARGUMENT, "null pointer");
   const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
-  preprocess_bwd_kernel<false><<<(P + 255) / 256, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
+  preprocess_bwd_kernel<false, false><<<(P + 255) / 256, 256, 0, st>>>(P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations,
                                                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x, focal_y,
                                                          tan_fovx, tan_fovy, nullptr, (float)width, (float)height, const_cast<float*>(dL_dmean2D),
                                                          const_cast<float*>(dL_dconic), nullptr, nullptr, dL_dmean3D, dL_dcov3D,
-                                                         dL_dscale, dL_drot, 0);
+                                                         dL_dscale, dL_drot, 0, nullptr, nullptr);
   LAUNCH_TRY("preprocess_bwd_kernel");
   return SEGS_OK;
+}
+
+int segs_debug_preprocess_backward_camera(int P, int width, int height, const float* means3D, const int* radii, const float* scales,
+                                          float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                          const float* viewmatrix, const float* projmatrix, float tan_fovx, float tan_fovy,
+                                          const float* dL_dmean2D, const float* dL_dconic, float* dL_dmean3D, float* dL_dcov3D,
+                                          float* dL_dscale, float* dL_drot, const float* dL_dz, const segs_camera_grads* camera_grads,
+                                          void* stream) {
+  if (!camera_grads)
+    return segs_debug_preprocess_backward(P, width, height, means3D, radii, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
+                                          projmatrix, tan_fovx, tan_fovy, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot,
+                                          stream);
+  hipStream_t st = (hipStream_t)stream;
+  bool cam_live = false;
+  if (int rc = camera_grads_begin(camera_grads, nullptr, P <= 0, st, &cam_live)) return rc;
+  if (P <= 0) return SEGS_OK;
+  if (!means3D || !radii || !viewmatrix || !projmatrix || !dL_dmean2D || !dL_dconic || !dL_dmean3D || !dL_dcov3D)
+    return fail(SEGS_ERR_INVALID_ARGUMENT, "null pointer");
+  const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
+  const int nblocks = (P + 255) / 256;
+  (dL_dz ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<false, true>)<<<nblocks, 256, 0, st>>>(
+      P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x,
+      focal_y, tan_fovx, tan_fovy, nullptr, (float)width, (float)height, const_cast<float*>(dL_dmean2D), const_cast<float*>(dL_dconic),
+      nullptr, nullptr, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, 0, dL_dz, camera_partials(camera_grads));
+  LAUNCH_TRY("preprocess_bwd_kernel");
+  return camera_grads_finish(camera_grads, nblocks, st);
 }
 
 int segs_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int n,
@@ -898,7 +971,7 @@ int segs_rasterize_backward_resident(char* geom_buffer, char* binning_buffer, ch
   return rasterize_backward_impl(P, D, M, capacity, background, width, height, means3D, shs, scales, scale_modifier, rotations,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
                                  image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                 dL_dscale, dL_drot, stream, true, geom_rows, nullptr);
+                                 dL_dscale, dL_drot, stream, true, geom_rows, nullptr, nullptr);
 }
 
 int segs_rasterize_backward_resident_depth(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P,
@@ -912,7 +985,21 @@ int segs_rasterize_backward_resident_depth(char* geom_buffer, char* binning_buff
   return rasterize_backward_impl(P, D, M, capacity, background, width, height, means3D, shs, scales, scale_modifier, rotations,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
                                  image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                 dL_dscale, dL_drot, stream, true, geom_rows, depth_grads);
+                                 dL_dscale, dL_drot, stream, true, geom_rows, depth_grads, nullptr);
+}
+
+int segs_rasterize_backward_resident_camera(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity, int geom_rows, int P,
+                                            int D, int M, const float* background, int width, int height, const float* means3D,
+                                            const float* shs, const float* scales, float scale_modifier, const float* rotations,
+                                            const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                            const float* campos, float tan_fovx, float tan_fovy, const int* radii, const float* dL_dpix,
+                                            float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                                            float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                            const segs_depth_grads* depth_grads, const segs_camera_grads* camera_grads, void* stream) {
+  return rasterize_backward_impl(P, D, M, capacity, background, width, height, means3D, shs, scales, scale_modifier, rotations,
+                                 cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+                                 image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                 dL_dscale, dL_drot, stream, true, geom_rows, depth_grads, camera_grads);
 }
 
 // ---- measurement support (bench.py): HIP events recorded on the launch stream around selected kernels.

@@ -36,7 +36,10 @@ __global__ void visible_filter_kernel(
 __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __restrict__ viewmatrix,
                                     uint8_t* __restrict__ present);
 
-template <bool DEPTH>   // DEPTH: + row dword [9] (dL/dz of the depth map, render_bwd_depth_kernel) into dL/dmean3D
+// DEPTH: + row dword [9] (dL/dz of the depth map, render_bwd_depth_kernel) into dL/dmean3D
+// CAM: + one row of 24 partial sums of dL/dviewmatrix and dL/dprojmatrix per workgroup into cam_partials (dz_in: see preprocess.hip)
+constexpr int CAM_SUMS = 24;   // 12 live entries of each 4x4 gradient
+template <bool DEPTH, bool CAM>
 __global__ void preprocess_bwd_kernel(
     int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,
     const float* __restrict__ rotations, float mod, const float* __restrict__ cov3D_precomp,
@@ -44,7 +47,10 @@ __global__ void preprocess_bwd_kernel(
     float* __restrict__ gacc, float img_w, float img_h,
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
-    float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int clean_gacc);
+    float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int clean_gacc,
+    const float* __restrict__ dz_in, float* __restrict__ cam_partials);
+__global__ void camera_grad_reduce_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ dL_dview,
+                                          float* __restrict__ dL_dproj);
 __global__ void sh_backward_kernel(int P, const float* __restrict__ means3D, const int* __restrict__ radii,
                                    const float* __restrict__ shs, int D, int M, const float* __restrict__ cam_pos,
                                    const uint32_t* __restrict__ clamped, const float* __restrict__ dL_dcolor,

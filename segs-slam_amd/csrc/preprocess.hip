@@ -6,6 +6,8 @@
 //   preprocess_bwd_kernel   K12+K13 fused; reference: computeCov2DCUDA backward.cu:144-274,
 //                           preprocessCUDA backward.cu:346-396, computeCov3D backward.cu:278-341
 //                           <true>: + the depth map's dL/dz (row dword [9]); no reference counterpart
+//                           <., true>: + the 24 per-workgroup sums of the camera gradient (dL/dviewmatrix, dL/dprojmatrix)
+//   camera_grad_reduce_kernel   sums those partials in a fixed order into the two 4x4 gradients; no reference counterpart
 //
 // All are HBM-bound streaming kernels (one Gaussian per lane, 256-thread workgroups):
 //  * the (P,3) AoS inputs are fetched as three fully coalesced dword sweeps per workgroup and
@@ -272,7 +274,15 @@ __device__ __forceinline__ void quat_rows(float4 q, float R[3][3]) {   // standa
 // DEPTH (after render_bwd_depth_kernel): row dword [9] holds dL/dz of the view-space depth z = V[2] x + V[6] y + V[10] z + V[14]
 // that the depth map composites, which adds dL/dz (V[2], V[6], V[10]) to dL/dmean3D.  A template KERNEL, not a kernel wrapping
 // an inlined body: the wrapped form of <false> came out with 92 instead of 86 VGPRs.
-template <bool DEPTH>
+// CAM: the gradient with respect to the two camera matrices, taken as independent inputs in their transposed layout
+// (t_i = sum_j view[4 j + i] p_j + view[12 + i]).  Per binned Gaussian, with dt = (dtx, dty, dtz [+ dz]):
+//   dL/dview[12 + i] += dt_i                 dL/dview[4 j + i] += dt_i p_j + sum_r J[r][i] dM2[r][j]     (the Wv inside M2 = J Wv)
+//   dL/dproj[4 j + i] += dh_i p_j (p_3 = 1), dh = (g2x w, g2y w, 0, -(g2x hom.x + g2y hom.y) w^2)
+// 12 + 12 live sums (row 3 of view and column 2 of proj are structurally zero).  Each workgroup sums its 256 lanes on chip -- three
+// passes of eight values through the input sweeps' staging buffer, no LDS of its own -- and plain-stores 24 floats into
+// cam_partials[blockIdx.x]; camera_grad_reduce_kernel adds the workgroups' rows in a fixed order.  No atomics: the same
+// per-Gaussian inputs give the same bits.  dz_in (CAM only, gacc null): per-Gaussian dL/dz of the stage-alone debug entry.
+template <bool DEPTH, bool CAM>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
     int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,
     const float* __restrict__ rotations, float mod, const float* __restrict__ cov3D_precomp,
@@ -281,7 +291,8 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-    int clean_gacc /* write zeros back over the consumed accumulator row (resident backward) */) {
+    int clean_gacc /* write zeros back over the consumed accumulator row (resident backward) */,
+    const float* __restrict__ dz_in, float* __restrict__ cam_partials /* CAM: CAM_SUMS floats per workgroup */) {
   __shared__ float lds[3 * 768];
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const bool live = idx < P;
@@ -345,9 +356,12 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
   } else if (live) {
     g2x = dL_dmean2D[3 * (size_t)idx + 0]; g2y = dL_dmean2D[3 * (size_t)idx + 1];
     G.xx = dL_dconic[4 * (size_t)idx + 0]; G.xy = dL_dconic[4 * (size_t)idx + 1]; G.yy = dL_dconic[4 * (size_t)idx + 3];
+    if constexpr (CAM && DEPTH) { if (dz_in) dz = dz_in[idx]; }
   }
 
   float out_mean[3] = {0, 0, 0}, out_cov[6] = {0, 0, 0, 0, 0, 0}, out_scale[3] = {0, 0, 0}, out_rot[4] = {0, 0, 0, 0};
+  float cam[CAM ? CAM_SUMS : 1] = {0};   // CAM: view slots 3 j + i (i < 3, j < 4; j = 3 is the translation row), then proj slots
+                                         // 12 + 3 j + {x, y, w}; lanes without a binned Gaussian contribute zero
   if (binned) {
     // ---- forward quantities again (cheaper than storing them: 36 B of inputs against ~30 floats of intermediates)
     const float tx0 = view[0] * mean.x + view[4] * mean.y + view[8] * mean.z + view[12];
@@ -454,6 +468,22 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
 #pragma unroll
       for (int j = 0; j < 3; j++) out_mean[j] += dz * view[4 * j + 2];
     }
+    if constexpr (CAM) {
+      const float dtz_all = DEPTH ? dtz + dz : dtz;
+      const float pm[3] = {mean.x, mean.y, mean.z};
+      const float dh0 = g2x * w, dh1 = g2y * w, dh3 = -(g2x * hx + g2y * hy) * (w * w);
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        cam[3 * j + 0] = dtx * pm[j] + J00 * dM2[0][j];
+        cam[3 * j + 1] = dty * pm[j] + J11 * dM2[1][j];
+        cam[3 * j + 2] = dtz_all * pm[j] + (J02 * dM2[0][j] + J12 * dM2[1][j]);
+        cam[12 + 3 * j + 0] = dh0 * pm[j];
+        cam[12 + 3 * j + 1] = dh1 * pm[j];
+        cam[12 + 3 * j + 2] = dh3 * pm[j];
+      }
+      cam[9] = dtx; cam[10] = dty; cam[11] = dtz_all;
+      cam[21] = dh0; cam[22] = dh1; cam[23] = dh3;
+    }
     // ---- scales and rotation: dL/dL = 2 M2^T (Dc U)
     if (scales) {
       float DU[2][3];
@@ -478,6 +508,24 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
       out_rot[3] = 2.f * (r * (GR[1][0] - GR[0][1]) + x * (GR[0][2] + GR[2][0]) + y * (GR[1][2] + GR[2][1])) - 4.f * z * (GR[0][0] + GR[1][1]);
     }
   }
+  if constexpr (CAM) {
+    // eight values at a time: lds[v][256 lanes], then 32 lanes per value add eight entries each and finish with five shuffle
+    // steps -- every operand and the order of every addition are fixed by the lane numbering alone
+    const int v = threadIdx.x >> 5, l = threadIdx.x & 31;
+#pragma unroll
+    for (int pass = 0; pass < CAM_SUMS / 8; pass++) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) lds[k * 256 + threadIdx.x] = cam[pass * 8 + k];
+      __syncthreads();
+      float s = lds[v * 256 + l];
+#pragma unroll
+      for (int q = 1; q < 8; q++) s += lds[v * 256 + l + 32 * q];
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+      if (l == 0) cam_partials[(size_t)blockIdx.x * CAM_SUMS + pass * 8 + v] = s;
+      __syncthreads();
+    }
+  }
   if (gacc) store_row3(dL_dmean2D, P, lds, g2x, g2y, 0.f);
   store_row3(dL_dmean3D, P, lds, out_mean[0], out_mean[1], out_mean[2]);
   if (dL_dscale) store_row3(dL_dscale, P, lds, out_scale[0], out_scale[1], out_scale[2]);
@@ -490,10 +538,50 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
 }
 
 #define SEGS_PREPROCESS_BWD_ARGS int, const float*, const int*, const float*, const float*, float, const float*, const float*, \
-    const float*, float, float, float, float, float*, float, float, float*, float*, float*, float*, float*, float*, float*, float*, int
-template __global__ void preprocess_bwd_kernel<false>(SEGS_PREPROCESS_BWD_ARGS);
-template __global__ void preprocess_bwd_kernel<true>(SEGS_PREPROCESS_BWD_ARGS);
+    const float*, float, float, float, float, float*, float, float, float*, float*, float*, float*, float*, float*, float*, float*, int, \
+    const float*, float*
+template __global__ void preprocess_bwd_kernel<false, false>(SEGS_PREPROCESS_BWD_ARGS);
+template __global__ void preprocess_bwd_kernel<true, false>(SEGS_PREPROCESS_BWD_ARGS);
+template __global__ void preprocess_bwd_kernel<false, true>(SEGS_PREPROCESS_BWD_ARGS);
+template __global__ void preprocess_bwd_kernel<true, true>(SEGS_PREPROCESS_BWD_ARGS);
 #undef SEGS_PREPROCESS_BWD_ARGS
+
+// The workgroups' CAM_SUMS-float rows (preprocess_bwd_kernel<., true>) -> dL/dviewmatrix and dL/dprojmatrix, all 32 floats written.
+// ONE workgroup of 960 threads = 160 rows x 6 float4 per sweep: a thread keeps its float4 column and adds the rows r0, r0 + 160, ...
+// in that order, then 10 x 16 and 1 x 10 more additions through LDS -- a fixed tree, so the result does not depend on timing.
+__global__ void __launch_bounds__(960) camera_grad_reduce_kernel(const float* __restrict__ partials, int nblocks,
+                                                                 float* __restrict__ dL_dview, float* __restrict__ dL_dproj) {
+  __shared__ float rows[160 * CAM_SUMS];
+  __shared__ float mid[10 * CAM_SUMS];
+  __shared__ float sums[CAM_SUMS];
+  const int t = threadIdx.x, q = t % 6, r0 = t / 6;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 8
+  for (int r = r0; r < nblocks; r += 160) {
+    const float4 x = reinterpret_cast<const float4*>(partials + (size_t)r * CAM_SUMS)[q];
+    acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+  }
+  reinterpret_cast<float4*>(rows + r0 * CAM_SUMS)[q] = acc;
+  __syncthreads();
+  if (t < 10 * CAM_SUMS) {
+    const int v = t % CAM_SUMS, g = t / CAM_SUMS;
+    float s = 0.f;
+    for (int k = 0; k < 16; k++) s += rows[(16 * g + k) * CAM_SUMS + v];
+    mid[g * CAM_SUMS + v] = s;
+  }
+  __syncthreads();
+  if (t < CAM_SUMS) {
+    float s = 0.f;
+    for (int g = 0; g < 10; g++) s += mid[g * CAM_SUMS + t];
+    sums[t] = s;
+  }
+  __syncthreads();
+  if (t < 32) {
+    const int e = t & 15, i = e & 3, j = e >> 2;
+    if (t < 16) dL_dview[e] = i < 3 ? sums[3 * j + i] : 0.f;                            // dL/dview[4 j + 3] = 0
+    else dL_dproj[e] = i != 2 ? sums[12 + 3 * j + (i == 3 ? 2 : i)] : 0.f;              // column i = 2 never enters the render
+  }
+}
 
 // SH colour branch only (callers that pass `shs`; off the live SEGS-SLAM path): dL/dsh and the view-direction term of
 // dL/dmean3D from the summed dL/dcolor (backward.cu:390-391), as a pass of its own so that its tables stay out of the

@@ -4,6 +4,9 @@ GaussianRasterizationSettings, GaussianRasterizerFunction (autograd), rasterizeG
 GaussianRasterizer module keep the reference's names, argument order and error behaviour.
 GaussianRasterizerDepthFunction, rasterizeGaussiansWithDepth and GaussianRasterizer.forward_with_depth have no reference
 counterpart: the same render plus a differentiable depth map (sum z alpha T) and alpha map (1 - T_final).
+GaussianRasterizerCameraFunction, rasterizeGaussiansWithCameraGrad and GaussianRasterizer.forward_with_camera_grad (no reference
+counterpart either) take viewmatrix and projmatrix as tensor inputs of the autograd function, so that a loss on colour, depth or
+alpha also differentiates with respect to the camera (pose refinement, bundle adjustment of keyframe poses).
 """
 from __future__ import annotations
 
@@ -105,6 +108,50 @@ class GaussianRasterizerDepthFunction(torch.autograd.Function):
                 g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
 
 
+class GaussianRasterizerCameraFunction(torch.autograd.Function):
+    """GaussianRasterizerDepthFunction with viewmatrix and projmatrix as differentiable inputs: two independent (4, 4) tensors in
+    the transposed layout, the ones of raster_settings being ignored (rasterize_points.RasterizeGaussiansCameraBackwardCUDA).
+    Precomputed colours only: the SH colours depend on campos, whose gradient is not provided."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
+                raster_settings):
+        rs = raster_settings
+        e = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        num_rendered, color, radii, depth, alpha, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansDepthCUDA(
+            rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3Ds_precomp,
+            viewmatrix, projmatrix, rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, e, 0, rs.campos_, rs.prefiltered_)
+        ctx.num_rendered = num_rendered
+        ctx.scale_modifier = rs.scale_modifier_
+        ctx.tanfovx, ctx.tanfovy = rs.tanfovx_, rs.tanfovy_
+        ctx.save_for_backward(rs.bg_, viewmatrix, projmatrix, rs.campos_, colors_precomp, means3D, scales, rotations,
+                              cov3Ds_precomp, radii, geomBuffer, binningBuffer, imgBuffer)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii=None, grad_depth=None, grad_alpha=None):
+        (bg, viewmatrix, projmatrix, campos, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii,
+         geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 10
+        if grad_out_color is None:
+            ref = grad_depth if grad_depth is not None else grad_alpha
+            grad_out_color = torch.zeros((3,) + tuple(ref.shape), dtype=torch.float32, device=means3D.device)
+        e = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, _dL_dsh, dL_dscales, dL_drotations, dL_dview,
+         dL_dproj) = rp.RasterizeGaussiansCameraBackwardCUDA(
+            bg, means3D, radii, colors_precomp, scales, rotations, ctx.scale_modifier, cov3Ds_precomp, viewmatrix,
+            projmatrix, ctx.tanfovx, ctx.tanfovy, grad_out_color.contiguous(),
+            grad_depth.contiguous() if grad_depth is not None else None,
+            grad_alpha.contiguous() if grad_alpha is not None else None, e, 0, campos, geomBuffer,
+            ctx.num_rendered, binningBuffer, imgBuffer)
+        g = lambda t, ref: t if ref.numel() != 0 else None  # noqa: E731
+        return (dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, g(dL_dscales, scales), g(dL_drotations, rotations),
+                g(dL_dcov3D, cov3Ds_precomp), dL_dview.to(viewmatrix.dtype), dL_dproj.to(projmatrix.dtype), None)
+
+
 def rasterizeGaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
     """include/gaussian_rasterizer.h:79-101."""
     return GaussianRasterizerFunction.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
@@ -115,6 +162,15 @@ def rasterizeGaussiansWithDepth(means3D, means2D, sh, colors_precomp, opacities,
     """rasterizeGaussians plus the depth and alpha maps: -> (color (3,H,W), radii (P), depth (H,W), alpha (H,W))."""
     return GaussianRasterizerDepthFunction.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                                  cov3Ds_precomp, raster_settings)
+
+
+def rasterizeGaussiansWithCameraGrad(means3D, means2D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
+                                     projmatrix, raster_settings):
+    """rasterizeGaussiansWithDepth with the two camera matrices as differentiable (4, 4) tensor inputs (transposed layout; the
+    ones inside raster_settings are not used): -> (color (3,H,W), radii (P), depth (H,W), alpha (H,W)).  After backward(),
+    viewmatrix.grad / projmatrix.grad -- or whatever pose parameters produced them -- are filled."""
+    return GaussianRasterizerCameraFunction.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                                  viewmatrix, projmatrix, raster_settings)
 
 
 class GaussianRasterizer(torch.nn.Module):
@@ -164,6 +220,20 @@ class GaussianRasterizer(torch.nn.Module):
         cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
         return rasterizeGaussiansWithDepth(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                            self.raster_settings_)
+
+    def forward_with_camera_grad(self, means3D, means2D, opacities, has_scales, has_rotations, has_cov3D_precomp, colors_precomp,
+                                 scales=None, rotations=None, cov3D_precomp=None, viewmatrix=None, projmatrix=None):
+        """forward_with_depth() differentiable with respect to the camera too: viewmatrix / projmatrix (default: the settings'
+        tensors) are inputs of the autograd graph.  Precomputed colours only.  -> (color, radii, depth, alpha)."""
+        self._check(False, True, has_scales, has_rotations, has_cov3D_precomp)
+        rs = self.raster_settings_
+        e = self._absent(means3D)
+        scales = scales if has_scales else e
+        rotations = rotations if has_rotations else e
+        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        return rasterizeGaussiansWithCameraGrad(means3D, means2D, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                                rs.viewmatrix_ if viewmatrix is None else viewmatrix,
+                                                rs.projmatrix_ if projmatrix is None else projmatrix, rs)
 
     def visible_filter(self, means3D, has_scales, has_rotations, has_cov3D_precomp, scales=None, rotations=None,
                        cov3D_precomp=None):

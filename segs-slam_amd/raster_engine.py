@@ -52,13 +52,17 @@ class RasterEngine:
     reports an overflow if R ever outgrew it.
 
     render_depth=True: every forward also fills out_depth (sum z alpha T) and out_alpha (1 - T_final), both (H, W) and
-    allocated here once, through the `_depth` twins of the entry points; backward() then takes their gradients too."""
+    allocated here once, through the `_depth` twins of the entry points; backward() then takes their gradients too.
+
+    camera_grad=True: every backward() also fills dL_dviewmatrix and dL_dprojmatrix, the (4, 4) gradients with respect to the
+    two camera matrices of the last forward (each an independent input, transposed layout), through the `_camera` backwards."""
 
     def __init__(self, P: int, width: int, height: int, device="cuda:0", resident: bool = False,
                  skip_nonpositive_opacity: bool = False, keep_dead_instances: bool = False, want_cov3D_grad: bool = False,
-                 render_depth: bool = False):
+                 render_depth: bool = False, camera_grad: bool = False):
         self.resident = bool(resident)
         self.render_depth = bool(render_depth)
+        self.camera_grad = bool(camera_grad)
         # SEGS_RASTER_SKIP_NONPOSITIVE_OPACITY (segs_raster.h): candidate-domain inputs of segs_neural_forward
         # SEGS_RASTER_KEEP_DEAD_INSTANCES: resident forwards bin the reference's full bounding squares (R == R_reference)
         self.flags = (1 if skip_nonpositive_opacity else 0) | (2 if keep_dead_instances else 0)
@@ -92,6 +96,13 @@ class RasterEngine:
         self.R = 0
         self._lib = _capi.lib()
         self._last = None
+        self.dL_dviewmatrix = torch.zeros((4, 4), **f) if self.camera_grad else None
+        self.dL_dprojmatrix = torch.zeros((4, 4), **f) if self.camera_grad else None
+        self._camera_out = None
+        if self.camera_grad:    # the partial rows of the per-Gaussian backward's workgroups, sized for all P rows once
+            self._camera_temp = torch.empty(self._lib.segs_camera_grad_temp_bytes(self.P), dtype=torch.uint8, device=self.device)
+            self._camera_out = _capi.CameraGrads(self.dL_dviewmatrix.data_ptr(), self.dL_dprojmatrix.data_ptr(),
+                                                 self._camera_temp.data_ptr())
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -250,9 +261,14 @@ class RasterEngine:
         self._last_resident = True
         return self.out_color
 
-    def backward(self, dL_dout_color: torch.Tensor, dL_ddepth: torch.Tensor = None, dL_dalpha: torch.Tensor = None):
+    def backward(self, dL_dout_color: torch.Tensor, dL_ddepth: torch.Tensor = None, dL_dalpha: torch.Tensor = None,
+                 camera_grad: bool = None):
         """Gradients land in self.grads (views of self.grads_flat), dL_dmean2D, dL_dcov3D.  dL_ddepth / dL_dalpha (H, W; None =
-        zero) are the gradients of out_depth / out_alpha of a render_depth engine."""
+        zero) are the gradients of out_depth / out_alpha of a render_depth engine.  A camera_grad engine also fills
+        dL_dviewmatrix / dL_dprojmatrix; camera_grad=False skips that for one call (the plain or depth backward)."""
+        camera_out = self._camera_out if (camera_grad is None or camera_grad) else None
+        if camera_grad and camera_out is None:
+            raise ValueError("camera gradients need an engine made with camera_grad=True")
         (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
          scale_modifier) = self._last
         assert dL_dout_color.is_contiguous() and dL_dout_color.dtype == torch.float32
@@ -272,7 +288,11 @@ class RasterEngine:
                     p(means3D), None, p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix), p(campos),
                     float(tanfovx), float(tanfovy), p(self.radii), p(dL_dout_color), p(self.dL_dmean2D), None,
                     p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]), p(g["rotations"]))
-            if depth_grads is not None:
+            if camera_out is not None:
+                st = self._lib.segs_rasterize_backward_resident_camera(*args, C.byref(depth_grads) if depth_grads is not None else None,
+                                                                       C.byref(camera_out), self._stream())
+                _capi.check(st, "segs_rasterize_backward_resident_camera")
+            elif depth_grads is not None:
                 st = self._lib.segs_rasterize_backward_resident_depth(*args, C.byref(depth_grads), self._stream())
                 _capi.check(st, "segs_rasterize_backward_resident_depth")
             else:
@@ -284,7 +304,11 @@ class RasterEngine:
                 p(self.geom.tensor), p(self.binning.tensor), p(self.img.tensor), p(dL_dout_color), p(self.dL_dmean2D),
                 None, p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]),
                 p(g["rotations"]))
-        if depth_grads is not None:
+        if camera_out is not None:
+            st = self._lib.segs_rasterize_backward_camera(*args, C.byref(depth_grads) if depth_grads is not None else None,
+                                                          C.byref(camera_out), self._stream())
+            _capi.check(st, "segs_rasterize_backward_camera")
+        elif depth_grads is not None:
             st = self._lib.segs_rasterize_backward_depth(*args, C.byref(depth_grads), self._stream())
             _capi.check(st, "segs_rasterize_backward_depth")
         else:

@@ -14,6 +14,10 @@ and, with no reference counterpart, the pair that also renders a depth and an al
 
   RasterizeGaussiansDepthCUDA / RasterizeGaussiansDepthBackwardCUDA
 
+and the backward that also returns the gradients with respect to the two camera matrices (segs_rasterize_backward_camera):
+
+  RasterizeGaussiansCameraBackwardCUDA
+
 torch is plumbing only here (device memory + current stream); every kernel is in csrc/.
 """
 from __future__ import annotations
@@ -223,6 +227,52 @@ def RasterizeGaussiansDepthBackwardCUDA(background, means3D, radii, colors, scal
                 _ptr(dL_drotations) if has_sr else None, C.byref(dg), _stream(dev))
         _capi.check(st, "segs_rasterize_backward_depth")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+def RasterizeGaussiansCameraBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                                         viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_alpha,
+                                         sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer):
+    """RasterizeGaussiansDepthBackwardCUDA plus the gradients with respect to viewmatrix and projmatrix, each taken as an
+    independent (4, 4) input in its transposed layout (include/segs_raster.h, segs_rasterize_backward_camera).  `sh` must be
+    absent: the SH colours depend on campos, which these gradients do not cover.
+    -> the depth backward's tuple + (dL_dviewmatrix (4,4), dL_dprojmatrix (4,4))."""
+    _require_gpu(means3D, "means3D")
+    dev = means3D.device
+    P, H, W = int(means3D.size(0)), int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    opts = dict(dtype=torch.float32, device=dev)
+    dL_dmeans3D = torch.empty((P, 3), **opts)
+    dL_dmeans2D = torch.empty((P, 3), **opts)
+    dL_dcolors = torch.empty((P, NUM_CHANNELS), **opts)
+    dL_dopacity = torch.empty((P, 1), **opts)
+    dL_dcov3D = torch.empty((P, 6), **opts)
+    dL_dsh = torch.zeros((P, M, 3), **opts)
+    has_sr = scales.numel() != 0
+    dL_dscales = torch.empty((P, 3), **opts) if has_sr else torch.zeros((P, 3), **opts)
+    dL_drotations = torch.empty((P, 4), **opts) if has_sr else torch.zeros((P, 4), **opts)
+    dL_dview = torch.empty((4, 4), **opts)     # the library writes all 32 floats, zeros when nothing is rendered
+    dL_dproj = torch.empty((4, 4), **opts)
+    gD = _depth_grad_ptr(dL_dout_depth, H, W, "dL_dout_depth")
+    gA = _depth_grad_ptr(dL_dout_alpha, H, W, "dL_dout_alpha")
+    gD, gA = (_f32c(t) if t is not None else None for t in (gD, gA))
+    keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
+                               projmatrix, campos, dL_dout_color)]
+    bg, m3, shc, col, sca, rot, cov, view, proj, cam, dL = keep
+    rad = radii.contiguous()
+    lib = _capi.lib()
+    temp = torch.empty(lib.segs_camera_grad_temp_bytes(P), dtype=torch.uint8, device=dev)
+    dg = _capi.DepthGrads(gD.data_ptr() if gD is not None else None, gA.data_ptr() if gA is not None else None)
+    cg = _capi.CameraGrads(dL_dview.data_ptr(), dL_dproj.data_ptr(), temp.data_ptr())
+    with torch.cuda.device(dev):     # called for P == 0 too: the library zero-fills the two matrices
+        st = lib.segs_rasterize_backward_camera(
+            P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sca),
+            float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx),
+            float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL),
+            _ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dmeans3D),
+            _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
+            _ptr(dL_drotations) if has_sr else None, C.byref(dg), C.byref(cg), _stream(dev))
+    _capi.check(st, "segs_rasterize_backward_camera")
+    return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview, dL_dproj)
 
 
 def markVisible(means3D, viewmatrix, projmatrix):
