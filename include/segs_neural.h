@@ -54,7 +54,8 @@ uint32_t segs_neural_set_flags(uint32_t flags);
 int segs_neural_param_layout(const segs_neural_dims* dims, int64_t* offsets, int64_t* counts, int* ntensors, int64_t* total);
 
 /* Bytes of device scratch shared by forward and backward for A anchors (visible list, operand images of the MLP weights,
- * per-workgroup partial sums of the weight gradients; per-anchor scratch rows only for the feature bank's two Linears).
+ * per-workgroup partial sums of the weight gradients and of segs_neural_backward_camera's camera-centre gradient; per-anchor
+ * scratch rows only for the feature bank's two Linears).
  * A <= 8 000 000 (the kernels index with 32-bit element offsets; SEGS_ERR_UNSUPPORTED beyond). */
 size_t segs_neural_temp_bytes(const segs_neural_dims* dims, int A);
 
@@ -106,6 +107,27 @@ int segs_neural_backward(const segs_neural_dims* dims, int A, const float* ancho
                          const float* dL_drotations, float* dL_danchor, float* dL_doffset, float* dL_dfeat,
                          float* dL_dscaling_log, float* dL_dmlp_params, float scaling_reg_weight, float* scaling_reg_out,
                          char* temp, void* stream);
+
+/* segs_neural_backward that also gives the gradient with respect to the camera centre.  Every colour, opacity, scale and
+ * rotation is an MLP output of view = (anchor - camera_center) / dist and dist = |anchor - camera_center|
+ * (src/gaussian_renderer.cpp:232-251; with the feature bank also through bank_weight), so with dview / ddist the first-layer
+ * input gradients of the three MLPs plus the feature-bank MLP,
+ *     g_a = (dview - view (view . dview)) / dist + ddist * view            per visible anchor a,
+ *     dL_dcamera_center = - sum over the visible anchors of g_a.
+ * The xyz = anchor + offset * scaling path does not depend on the camera and is not in it.  pose7 is a CONSTANT: the
+ * reference builds it from host floats (:258-264), no gradient flows to the camera through the appearance embedding.
+ * The visible anchors are those of the forward call (segs_neural_forward or segs_neural_forward_projected) whose `temp`
+ * this is.  dL_dcamera_center: 3 device floats, OVERWRITTEN (not accumulated; zero when no anchor is visible), the same
+ * bits on every call with the same inputs (no float atomics on this path).  NULL: exactly segs_neural_backward.  All
+ * other arguments and outputs are segs_neural_backward's, bit for bit.  Join it with dL_dviewmatrix / dL_dprojmatrix of
+ * segs_rasterize_backward[_resident]_camera (segs_raster.h) for the gradient of a pose: INTEGRATION.md. */
+int segs_neural_backward_camera(const segs_neural_dims* dims, int A, const float* anchor, const float* offset,
+                                const float* anchor_feat, const float* scaling_log, const float* mlp_params,
+                                const float* camera_center, const float* pose7, const float* dL_dmeans3D,
+                                const float* dL_dcolors, const float* dL_dopacity, const float* dL_dscales,
+                                const float* dL_drotations, float* dL_danchor, float* dL_doffset, float* dL_dfeat,
+                                float* dL_dscaling_log, float* dL_dmlp_params, float scaling_reg_weight,
+                                float* scaling_reg_out, float* dL_dcamera_center, char* temp, void* stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ constexpr int WG_WAVES = 256;  // waves per weight-gradient job
 constexpr int WG_UNROLL = 8;   // row pairs whose operand loads are in flight together
 constexpr int WG_JOBS = 8;
 constexpr int WG_TILE = 2 * 3 * 1024;  // floats of partial sums per (job, wave): up to 2x3 tiles of 32x32
+constexpr size_t PARTIAL_FLOATS = (size_t)WG_JOBS * WG_WAVES * WG_TILE;   // all partial tiles; the camera backward's rows follow them
 constexpr int MAX_APP = 64;
 constexpr int MAX_ANCHORS = 8000000;   // 32-bit element offsets: A * ROW and A * 40 stay below 2^32
 
@@ -112,18 +113,19 @@ struct Temp {             // carve-up of the caller's scratch
   float* gsum;            // [total + pad] this call's parameter-gradient sums
   float* images;          // [N_IMG_BWD][64] MFMA A-operand images of the MLP weights (built by the forward call)
   void* small;            // Small tables
+  float4* cam_rows;       // [BWD_GRID] per-workgroup partial sums of dL/dcamera_center (segs_neural_backward_camera): follows `partial`
 };
 size_t temp_carve(int A, int total, int bank, char* base, Temp* t) {
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
   // scratch rows: only the feature bank's two small Linears still take their weight gradients from them (2 KB per anchor)
   const size_t o_count = take(256), o_vis = take((size_t)A * 4), o_rows = take(bank ? (size_t)A * ROW * 4 : 256),
-               o_part = take((size_t)WG_JOBS * WG_WAVES * WG_TILE * 4), o_gsum = take((size_t)(total + 64) * 4),
+               o_part = take((PARTIAL_FLOATS + 256 * 4) * 4), o_gsum = take((size_t)(total + 64) * 4),
                o_img = take((size_t)262 * 64 * 4), o_small = take(8192);
   if (t) {
     t->count = (uint32_t*)(base + o_count); t->vis = (uint32_t*)(base + o_vis); t->rows = (float*)(base + o_rows);
     t->partial = (float*)(base + o_part); t->gsum = (float*)(base + o_gsum);
-    t->images = (float*)(base + o_img); t->small = (void*)(base + o_small);
+    t->images = (float*)(base + o_img); t->small = (void*)(base + o_small); t->cam_rows = (float4*)(t->partial + PARTIAL_FLOATS);
   }
   return off;
 }
@@ -898,7 +900,14 @@ __device__ __forceinline__ void finish_mlp(const float* __restrict__ img, const 
   }
 }
 
-template <bool BANK>
+// CAM (both backward families): the workgroup also sums  -g_a  over its anchors, g_a = dL/d(anchor - camera centre) through
+// view and dist (the two last terms of dL/danchor below; the xyz = anchor + offset * scaling path does not see the camera).
+// Lane h == 0 of an anchor keeps three accumulators over the workgroup's whole persistent loop; after the loop the lanes of a
+// wave are added by a butterfly, the waves through four LDS slots behind the staging area, both in a fixed order, and the
+// workgroup's row goes to cam_rows[blockIdx.x] with one 16-byte store.  camera_center_reduce_kernel adds the rows that exist.
+// cam_rows is the [BWD_GRID][4] block that follows the partial tiles in the caller's scratch (temp_carve), so the kernels keep
+// their argument list and the plain instantiations (CAM = false) their code.
+template <bool BANK, bool CAM = false>
 __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
     Layout L, const uint32_t* __restrict__ count, const uint32_t* __restrict__ vis, const float* __restrict__ anchor,
     const float* __restrict__ offset, const float* __restrict__ anchor_feat, const float* __restrict__ scaling_log,
@@ -928,6 +937,7 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
   float sm[N_SMALL];    // [0..4] bias sums of the output tiles, [5..7] of the hidden layers, [8 + 4m + c] tail column c of MLP m
 #pragma unroll
   for (int q = 0; q < N_SMALL; q++) sm[q] = 0.f;
+  float cam[3] = {0.f, 0.f, 0.f};   // CAM: -sum of g_a over this lane's anchors, all rounds
 
   for (uint32_t g0 = (blockIdx.x * 4u + wv) * 32u; g0 < n; g0 += gridDim.x * 128u) {
     const uint32_t t = g0 + col;
@@ -1195,6 +1205,11 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
                           acc_anc[1] + danc[1] + (dview[1] - vy * dot) * st.inv_dist + dview[3] * vy,
                           acc_anc[2] + danc[2] + (dview[2] - vz * dot) * st.inv_dist + dview[3] * vz};
       stn<3>(d_anchor + a * 3, v);
+      if (CAM) {
+        cam[0] -= (dview[0] - vx * dot) * st.inv_dist + dview[3] * vx;
+        cam[1] -= (dview[1] - vy * dot) * st.inv_dist + dview[3] * vy;
+        cam[2] -= (dview[2] - vz * dot) * st.inv_dist + dview[3] * vz;
+      }
     }
   }
 
@@ -1204,6 +1219,15 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
   float* const stage = lds_dyn;                       // [4 waves][max(1024, N_SMALL * 64)] floats
   constexpr int STAGE = N_SMALL * 64 > 1024 ? N_SMALL * 64 : 1024;
   const int tid = threadIdx.x;
+  float* const cam_slot = stage + 4 * STAGE;          // CAM: [4 waves][4] behind the staging area (the barriers below order it)
+  if (CAM) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) cam[c] += __shfl_xor(cam[c], off, 64);
+      if (lane == 0) cam_slot[wv * 4 + c] = cam[c];
+    }
+  }
   auto slot = [&](int job) { return partial + ((size_t)job * WG_WAVES + blockIdx.x) * WG_TILE; };
 #pragma unroll 1
   for (int k = 0; k < 8; k++) {
@@ -1246,6 +1270,9 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
       slot(mm)[((1 * 3 + 0) * 32 + c) * 32 + u] = sum;
     }
   }
+  if (CAM && tid == 0)
+    reinterpret_cast<float4*>(partial + PARTIAL_FLOATS)[blockIdx.x] = make_float4((cam_slot[0] + cam_slot[4]) + (cam_slot[8] + cam_slot[12]), (cam_slot[1] + cam_slot[5]) + (cam_slot[9] + cam_slot[13]),
+                                       (cam_slot[2] + cam_slot[6]) + (cam_slot[10] + cam_slot[14]), 0.f);
 }
 
 // ---- the plain model's backward: chain waves and weight-gradient waves ------------------------------------------------
@@ -1269,7 +1296,10 @@ constexpr int PAIR_STAGE = 8 * 1024 + N_SMALL * 64;   // end of kernel: a wgrad 
 // softmax to the bank's two small Linears 4 -> 32 -> 3; only THEIR weight gradients still go through per-anchor scratch rows
 // (103 of the row's 512 floats) to wgrad_mfma_kernel.  Until round 4 this model ran the one-kernel form: 240 + 91 us at 200 k
 // anchors against 153 us for the plain model's pairs.
-template <bool BANK>
+// CAM: see neural_bwd_body.  The chain waves hold the accumulators; their four LDS slots lie behind the wgrad waves' staging
+// area (the camera launch asks for PAIR_CAM_LDS bytes more), which the operand images and tiles of the run do not reach.
+constexpr int PAIR_CAM_LDS = 16 * 4;
+template <bool BANK, bool CAM = false>
 __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
     Layout L, const uint32_t* __restrict__ count, const uint32_t* __restrict__ vis, const float* __restrict__ anchor,
     const float* __restrict__ offset, const float* __restrict__ anchor_feat, const float* __restrict__ scaling_log,
@@ -1278,6 +1308,8 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
     const float* __restrict__ g_scales, const float* __restrict__ g_rot, float* __restrict__ d_anchor,
     float* __restrict__ d_offset, float* __restrict__ d_feat, float* __restrict__ d_scaling_log, float* __restrict__ rows,
     float* __restrict__ partial, float reg_weight, float* __restrict__ reg_sum) {
+  static_assert((N_IMG_BWD * 64 + 4 * PAIR_LDS) * sizeof(float) + sizeof(Small) <= (size_t)4 * PAIR_STAGE * sizeof(float),
+                "the camera slots follow the staging area");
   extern __shared__ __align__(16) float lds_dyn[];
   float* img = lds_dyn;
   Small& S = *reinterpret_cast<Small*>(lds_dyn + N_IMG_BWD * 64);
@@ -1306,6 +1338,7 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
     // cost more than the round trips -- 0.24 -> 0.30-0.37 ms, profiles/r03_neural_bwd_pair_notes.txt.)
     auto slab_lane = [&](uint32_t rd) { return (rd * gridDim.x + blockIdx.x) * 128u + (uint32_t)pair * 32u + (uint32_t)col; };
     uint32_t a_nx = a_first;
+    float cam[3] = {0.f, 0.f, 0.f};   // CAM: -sum of g_a over this lane's anchors, all rounds
     for (uint32_t rd = 0; rd < rounds; rd++) {
       const uint32_t t = slab_lane(rd);
       const bool valid = t < n;   // a pair's last round may be empty: it runs on a copy of the last anchor and stores nothing
@@ -1592,6 +1625,19 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
                             acc_anc[1] + danc[1] + (dtail[1] - vy * dot) * st.inv_dist + dtail[3] * vy,
                             acc_anc[2] + danc[2] + (dtail[2] - vz * dot) * st.inv_dist + dtail[3] * vz};
         stn<3>(d_anchor + a * 3, v);
+        if (CAM) {
+          cam[0] -= (dtail[0] - vx * dot) * st.inv_dist + dtail[3] * vx;
+          cam[1] -= (dtail[1] - vy * dot) * st.inv_dist + dtail[3] * vy;
+          cam[2] -= (dtail[2] - vz * dot) * st.inv_dist + dtail[3] * vz;
+        }
+      }
+    }
+    if (CAM) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cam[c] += __shfl_xor(cam[c], off, 64);
+        if (lane == 0) stage[4 * PAIR_STAGE + pair * 4 + c] = cam[c];
       }
     }
     __syncthreads();   // every wave is done with the operand images and the tiles
@@ -1658,6 +1704,30 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
       slot(mm)[((1 * 3 + 0) * 32 + c) * 32 + u] = sum;
     }
   }
+  if (CAM && tid == 0) {
+    const float* const cs = stage + 4 * PAIR_STAGE;
+    reinterpret_cast<float4*>(partial + PARTIAL_FLOATS)[blockIdx.x] = make_float4((cs[0] + cs[4]) + (cs[8] + cs[12]), (cs[1] + cs[5]) + (cs[9] + cs[13]), (cs[2] + cs[6]) + (cs[10] + cs[14]), 0.f);
+  }
+}
+
+// dL/dcamera_center = the sum of the rows the backward's workgroups wrote (cam_rows[w] exists iff workgroup w had a slab, as
+// the weight-gradient partials: wgrad_reduce_kernel's nparts), one wave, fixed order; OVERWRITES out[0..2].  No visible
+// anchor: no row, zero.
+__global__ void __launch_bounds__(64) camera_center_reduce_kernel(const uint32_t* __restrict__ count, const float4* __restrict__ cam_rows,
+                                                                  float* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const int nparts = (int)min((uint32_t)BWD_GRID, (count[0] + 127u) / 128u);
+  float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < BWD_GRID / 64; u++) {
+    const int r = lane + 64 * u;
+    if (r < nparts) { const float4 v = cam_rows[r]; s[0] += v.x; s[1] += v.y; s[2] += v.z; }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_xor(s[c], off, 64);
+  if (lane < 3) out[lane] = lane == 0 ? s[0] : (lane == 1 ? s[1] : s[2]);
 }
 
 // ---- weight gradients ---------------------------------------------------------------------------------------------
@@ -1888,7 +1958,7 @@ static int neural_forward_impl(const segs_neural_dims* dims, int A, const float*
     return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, "invalid argument (null pointer or bad size)");
   Temp T;
   temp_carve(A, L.total, L.bank, temp, &T);
-  static_assert(N_IMG_BWD == 262 && sizeof(Small) <= 8192, "temp_carve sizes");
+  static_assert(N_IMG_BWD == 262 && sizeof(Small) <= 8192 && BWD_GRID == 256, "temp_carve sizes");
   // T.count: [0] visible anchors, [1] kept candidates; cleared (with the regulariser sum) by pack_tables_kernel
   pack_tables_kernel<<<(N_IMG_BWD * 64 + 255) / 256 + 1, 256, 0, st>>>(L, mlp_params, pose7, T.images, (Small*)T.small, T.count, T.gsum + L.total + 8);
   const bool small_map = A < 131072;
@@ -1953,19 +2023,26 @@ int segs_neural_forward_projected(const segs_neural_dims* dims, int A, const flo
                              nullptr, nullptr, scales, rotations, neural_opacity, temp, stream, tg, &pj, anchor_rotations, visible_radii);
 }
 
-int segs_neural_backward(const segs_neural_dims* dims, int A, const float* anchor, const float* offset, const float* anchor_feat,
-                         const float* scaling_log, const float* mlp_params, const float* camera_center, const float* pose7,
-                         const float* dL_dmeans3D, const float* dL_dcolors, const float* dL_dopacity, const float* dL_dscales,
-                         const float* dL_drotations, float* dL_danchor, float* dL_doffset, float* dL_dfeat,
-                         float* dL_dscaling_log, float* dL_dmlp_params, float scaling_reg_weight, float* scaling_reg_out, char* temp,
-                         void* stream) {
+// dL_dcamera_center == nullptr: segs_neural_backward, the launches it always made
+static int neural_backward_impl(const segs_neural_dims* dims, int A, const float* anchor, const float* offset, const float* anchor_feat,
+                                const float* scaling_log, const float* mlp_params, const float* camera_center, const float* pose7,
+                                const float* dL_dmeans3D, const float* dL_dcolors, const float* dL_dopacity, const float* dL_dscales,
+                                const float* dL_drotations, float* dL_danchor, float* dL_doffset, float* dL_dfeat,
+                                float* dL_dscaling_log, float* dL_dmlp_params, float scaling_reg_weight, float* scaling_reg_out,
+                                float* dL_dcamera_center, char* temp, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   Layout L;
   int rc = make_layout(dims, &L, nullptr, nullptr, nullptr);
   if (rc != SEGS_OK) return rc;
   if (A < 0) return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, "invalid argument (null pointer or bad size)");
   if (A > MAX_ANCHORS) return segs::set_error(SEGS_ERR_UNSUPPORTED, "more than 8 M anchors (the kernels index with 32-bit element offsets)");
-  if (A == 0) return SEGS_OK;
+  if (A == 0) {   // no anchor is no visible anchor: the camera gradient is overwritten with zero
+    if (dL_dcamera_center) {
+      const hipError_t e0 = hipMemsetAsync(dL_dcamera_center, 0, 3 * sizeof(float), st);
+      if (e0 != hipSuccess) return segs::set_hip_error(e0, __func__);
+    }
+    return SEGS_OK;
+  }
   if (!anchor || !offset || !anchor_feat || !scaling_log || !mlp_params || !camera_center || !dL_dmeans3D || !dL_dcolors ||
       !dL_dopacity || !dL_dscales || !dL_drotations || !dL_danchor || !dL_doffset || !dL_dfeat || !dL_dscaling_log ||
       !dL_dmlp_params || !temp || (L.app > 0 && !pose7))
@@ -1975,7 +2052,8 @@ int segs_neural_backward(const segs_neural_dims* dims, int A, const float* ancho
   constexpr size_t bwd_lds = (N_IMG_BWD * 64 + 4 * WAVE_LDS) * sizeof(float) + sizeof(Small);   // > 64 KB: needs the opt-in below
   constexpr size_t pair_run = (N_IMG_BWD * 64 + 4 * PAIR_LDS) * sizeof(float) + sizeof(Small), pair_end = (size_t)4 * PAIR_STAGE * sizeof(float);
   constexpr size_t pair_lds = pair_run > pair_end ? pair_run : pair_end;
-  static_assert(bwd_lds <= 160 * 1024 && pair_lds <= 160 * 1024, "one workgroup per CU");
+  static_assert(bwd_lds <= 160 * 1024 && pair_lds + PAIR_CAM_LDS <= 160 * 1024, "one workgroup per CU");
+  static_assert(pair_lds == pair_end, "the camera slots of the pair kernel follow the staging area");
   auto allow_lds = [](const void* kernel, size_t bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
   const hipError_t attr_rc[4] = {allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<false>), bwd_lds),
                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<true>), bwd_lds),
@@ -1983,6 +2061,15 @@ int segs_neural_backward(const segs_neural_dims* dims, int A, const float* ancho
                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<true>), pair_lds)};
   for (const hipError_t rc_attr : attr_rc)
     if (rc_attr != hipSuccess) return segs::set_hip_error(rc_attr, __func__);
+  const bool cam = dL_dcamera_center != nullptr;
+  if (cam) {
+    const hipError_t cam_rc[4] = {allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<false, true>), bwd_lds),
+                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<true, true>), bwd_lds),
+                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<false, true>), pair_lds + PAIR_CAM_LDS),
+                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<true, true>), pair_lds + PAIR_CAM_LDS)};
+    for (const hipError_t rc_attr : cam_rc)
+      if (rc_attr != hipSuccess) return segs::set_hip_error(rc_attr, __func__);
+  }
   // the regulariser sum was cleared by the forward (pack_tables_kernel) and is cleared again by reg_finish_kernel; it is
   // only accumulated when somebody reads it
   float* reg_sum = scaling_reg_out ? T.gsum + L.total + 8 : nullptr;
@@ -1990,7 +2077,17 @@ int segs_neural_backward(const segs_neural_dims* dims, int A, const float* ancho
   // compact rows).  SEGS_NEURAL_ONE_KERNEL_BACKWARD (segs_neural_set_flags, segs_neural.h) selects the one-kernel form: the
   // A/B of profiles/ and tests/test_neural_gpu.py.
   const bool one_role = (g_neural_flags & SEGS_NEURAL_ONE_KERNEL_BACKWARD) != 0u;
-  if (!one_role)
+  if (cam && !one_role)
+    (L.bank ? neural_bwd_pair_kernel<true, true> : neural_bwd_pair_kernel<false, true>)<<<BWD_GRID, 512, pair_lds + PAIR_CAM_LDS, st>>>(
+        L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
+        dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
+        scaling_reg_weight, reg_sum);
+  else if (cam)
+    (L.bank ? neural_bwd_kernel<true, true> : neural_bwd_kernel<false, true>)<<<BWD_GRID, 256, bwd_lds, st>>>(
+        L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
+        dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
+        scaling_reg_weight, reg_sum);
+  else if (!one_role)
     (L.bank ? neural_bwd_pair_kernel<true> : neural_bwd_pair_kernel<false>)<<<BWD_GRID, 512, pair_lds, st>>>(
         L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
@@ -2000,6 +2097,7 @@ int segs_neural_backward(const segs_neural_dims* dims, int A, const float* ancho
         L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
         scaling_reg_weight, reg_sum);
+  if (cam) camera_center_reduce_kernel<<<1, 64, 0, st>>>(T.count, T.cam_rows, dL_dcamera_center);
   if (scaling_reg_out && L.app == 0) reg_finish_kernel<<<1, 1, 0, st>>>(T.count, reg_sum, scaling_reg_weight, scaling_reg_out);
   const WJobs J = make_jobs(L, !one_role);
   if (L.bank) wgrad_mfma_kernel<<<dim3(WG_WAVES, WG_JOBS), WGM_WAVES * 64, 0, st>>>(J, T.count, T.rows, T.partial, one_role ? ROW : BROW);   // the feature bank's two small Linears
@@ -2008,6 +2106,28 @@ int segs_neural_backward(const segs_neural_dims* dims, int A, const float* ancho
                                                               scaling_reg_weight, scaling_reg_out);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SEGS_OK : segs::set_hip_error(e, __func__);
+}
+
+int segs_neural_backward(const segs_neural_dims* dims, int A, const float* anchor, const float* offset, const float* anchor_feat,
+                         const float* scaling_log, const float* mlp_params, const float* camera_center, const float* pose7,
+                         const float* dL_dmeans3D, const float* dL_dcolors, const float* dL_dopacity, const float* dL_dscales,
+                         const float* dL_drotations, float* dL_danchor, float* dL_doffset, float* dL_dfeat,
+                         float* dL_dscaling_log, float* dL_dmlp_params, float scaling_reg_weight, float* scaling_reg_out, char* temp,
+                         void* stream) {
+  return neural_backward_impl(dims, A, anchor, offset, anchor_feat, scaling_log, mlp_params, camera_center, pose7, dL_dmeans3D, dL_dcolors,
+                              dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, dL_dmlp_params,
+                              scaling_reg_weight, scaling_reg_out, nullptr, temp, stream);
+}
+
+int segs_neural_backward_camera(const segs_neural_dims* dims, int A, const float* anchor, const float* offset, const float* anchor_feat,
+                                const float* scaling_log, const float* mlp_params, const float* camera_center, const float* pose7,
+                                const float* dL_dmeans3D, const float* dL_dcolors, const float* dL_dopacity, const float* dL_dscales,
+                                const float* dL_drotations, float* dL_danchor, float* dL_doffset, float* dL_dfeat,
+                                float* dL_dscaling_log, float* dL_dmlp_params, float scaling_reg_weight, float* scaling_reg_out,
+                                float* dL_dcamera_center, char* temp, void* stream) {
+  return neural_backward_impl(dims, A, anchor, offset, anchor_feat, scaling_log, mlp_params, camera_center, pose7, dL_dmeans3D, dL_dcolors,
+                              dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, dL_dmlp_params,
+                              scaling_reg_weight, scaling_reg_out, dL_dcamera_center, temp, stream);
 }
 
 }  // extern "C"

@@ -279,20 +279,29 @@ class NeuralGaussians:
         """The reference's `mask` (neural_opacity > 0, src/gaussian_renderer.cpp:279) in the candidate domain."""
         return self.neural_opacity.view(-1)[:self.P] > 0
 
-    def backward(self, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, scaling_reg_weight: float = 0.0):
+    def backward(self, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, scaling_reg_weight: float = 0.0,
+                 camera_grad: bool = False):
         """Accumulates into model.grads.  scaling_reg_weight adds the mapper's 0.01 * mean(prod(scaling)) term
-        (src/gaussian_mapper.cpp:926-928); its value lands in self.scaling_reg."""
+        (src/gaussian_mapper.cpp:926-928); its value lands in self.scaling_reg.
+        camera_grad: segs_neural_backward_camera -- also OVERWRITES self.dL_dcamera_center (3 device floats, made once) with the
+        gradient through the generator's view direction and distance (segs_neural.h); pose7 is a constant."""
         if not hasattr(self, "scaling_reg"):
             self.scaling_reg = torch.zeros(1, dtype=torch.float32, device=self.model.device)
+        if camera_grad and not hasattr(self, "dL_dcamera_center"):
+            self.dL_dcamera_center = torch.zeros(3, dtype=torch.float32, device=self.model.device)
         m = self.model
         camera_center, pose7 = self._last
-        st = self._lib.segs_neural_backward(
-            C.byref(m._cdims), m.A, _p(m.param("anchor")), _p(m.param("offset")), _p(m.param("anchor_feat")),
-            _p(m.param("scaling")), _p(m.mlp_params), _p(camera_center), _p(pose7), _p(dL_dmeans3D), _p(dL_dcolors),
-            _p(dL_dopacity), _p(dL_dscales), _p(dL_drotations), _p(m.grad("anchor")), _p(m.grad("offset")),
-            _p(m.grad("anchor_feat")), _p(m.grad("scaling")), _p(m.mlp_grads), float(scaling_reg_weight),
-            _p(self.scaling_reg) if scaling_reg_weight else None, _p(self.temp), self._stream())
-        _capi.check(st, "segs_neural_backward")
+        head = (C.byref(m._cdims), m.A, _p(m.param("anchor")), _p(m.param("offset")), _p(m.param("anchor_feat")),
+                _p(m.param("scaling")), _p(m.mlp_params), _p(camera_center), _p(pose7), _p(dL_dmeans3D), _p(dL_dcolors),
+                _p(dL_dopacity), _p(dL_dscales), _p(dL_drotations), _p(m.grad("anchor")), _p(m.grad("offset")),
+                _p(m.grad("anchor_feat")), _p(m.grad("scaling")), _p(m.mlp_grads), float(scaling_reg_weight),
+                _p(self.scaling_reg) if scaling_reg_weight else None)
+        if camera_grad:
+            st = self._lib.segs_neural_backward_camera(*head, _p(self.dL_dcamera_center), _p(self.temp), self._stream())
+            _capi.check(st, "segs_neural_backward_camera")
+        else:
+            st = self._lib.segs_neural_backward(*head, _p(self.temp), self._stream())
+            _capi.check(st, "segs_neural_backward")
 
 
 @dataclass
@@ -341,7 +350,7 @@ class ScaffoldTrainerStep:
     all on the device without a host synchronisation in steady state."""
 
     def __init__(self, model: ScaffoldModel, width: int, height: int, opt: Optional[ScaffoldOptimizationParams] = None,
-                 spatial_lr_scale: float = 1.0, process_group=None, scaling_reg_weight: float = 0.0):
+                 spatial_lr_scale: float = 1.0, process_group=None, scaling_reg_weight: float = 0.0, pose_grad: bool = False):
         # scaling_reg_weight = 0.01 gives the mapper's loss (src/gaussian_mapper.cpp:926-928), 0 the trainer's (:89-90 of
         # src/gaussian_trainer.cpp); the mapper's FFT regularisers (:930-945): enable_frequency_regularization()
         self.scaling_reg_weight = float(scaling_reg_weight)
@@ -351,7 +360,12 @@ class ScaffoldTrainerStep:
         dev = model.device
         self._lib = model._lib
         self.neural = NeuralGaussians(model)
-        self.engine = RasterEngine(self.neural.P_capacity, width, height, dev, resident=True, skip_nonpositive_opacity=True)
+        # pose_grad: every iteration also leaves the gradient of its loss with respect to the keyframe's camera in `pose_grads`
+        # (camera forms of both backwards).  Local to the rank -- each rank has its own keyframe -- so it takes no
+        # part in the gradient exchange.
+        self.pose_grad = bool(pose_grad)
+        self.pose_grads = None
+        self.engine = self._make_engine(self.neural.P_capacity, width, height)
         self.loss_fn = FusedL1SSIM(height, width, dev, self.opt.lambda_dssim)
         # Gaussian-pyramid training (src/gaussian_mapper.cpp:837-858, 872-875, 913-915): a keyframe is trained at the size of
         # its current pyramid level, i.e. of the target image it hands over.  One rasterizer engine + loss object per size,
@@ -391,6 +405,7 @@ class ScaffoldTrainerStep:
         self.fuse_projection = True
         # the device drops an iteration whose forward overflowed the resident capacity; with one rank the host runs it again
         # before the next one (training_once), so no optimizer step of the reference's sequence is lost
+        # (`pose_grads` of an iteration the device dropped are meaningless, like its loss: the redo refills them)
         self.redo_dropped_steps = True
         self.redone_steps = 0
         self._last_iteration = None
@@ -398,6 +413,10 @@ class ScaffoldTrainerStep:
         self._graphs = {}
         self._graph_stage = {}
         self.graph_replays = 0
+
+    def _make_engine(self, P: int, width: int, height: int) -> RasterEngine:
+        return RasterEngine(P, width, height, self.model.device, resident=True, skip_nonpositive_opacity=True,
+                            camera_grad=self.pose_grad)
 
     def set_background(self, white: bool):
         """bg_color of GaussianMapper's constructor (src/gaussian_mapper.cpp:61-67)."""
@@ -524,8 +543,7 @@ class ScaffoldTrainerStep:
             return
         lv = self._levels.get(key)
         if lv is None:
-            lv = self._levels[key] = (RasterEngine(self.neural.P_capacity, key[0], key[1], self.model.device, resident=True,
-                                                   skip_nonpositive_opacity=True),
+            lv = self._levels[key] = (self._make_engine(self.neural.P_capacity, key[0], key[1]),
                                       FusedL1SSIM(key[1], key[0], self.model.device, self.opt.lambda_dssim))
         self._levels[(self.W, self.H)] = (self.engine, self.loss_fn)     # (a caller may have wrapped the current level's loss)
         self.engine, self.loss_fn = lv
@@ -534,8 +552,7 @@ class ScaffoldTrainerStep:
     def render(self, kf: Keyframe) -> torch.Tensor:
         ng = self.neural
         if self.model.capacity * self.model.dims.n_offsets > self.engine.P:   # the map outgrew the engines' buffers
-            self.engine = RasterEngine(self.model.capacity * self.model.dims.n_offsets, self.W, self.H, self.model.device,
-                                       resident=True, skip_nonpositive_opacity=True)
+            self.engine = self._make_engine(self.model.capacity * self.model.dims.n_offsets, self.W, self.H)
             self._levels = {(self.W, self.H): (self.engine, self.loss_fn)}   # the other levels' engines are re-made on use
             self.visible_radii = torch.zeros(self.model.capacity, dtype=torch.int32, device=self.model.device)
         self.engine.set_active(ng.P)
@@ -560,6 +577,7 @@ class ScaffoldTrainerStep:
             # (src/rasterize_points.cu:81) and nothing receives a gradient
             if exchange is not None:
                 exchange.reduce_flag_async(None, allow_piggyback=not flag_on_host)
+            self.pose_grads = None
             return self.loss_fn(torch.zeros(3, self.H, self.W, device=self.model.device), gt)[0]
         image = self.render(kf)
         if exchange is not None:
@@ -585,7 +603,28 @@ class ScaffoldTrainerStep:
         if mask is not None:
             dL = dL * mask
         g = self.engine.backward(dL)
-        self.neural.backward(g["means3D"], g["colors"], g["opacity"], g["scales"], g["rotations"], self.scaling_reg_weight)
+        self.neural.backward(g["means3D"], g["colors"], g["opacity"], g["scales"], g["rotations"], self.scaling_reg_weight,
+                             camera_grad=self.pose_grad)
+        if self.pose_grad:
+            # views of the current level's device buffers: valid until the next iteration, no host synchronisation
+            self.pose_grads = {"viewmatrix": self.engine.dL_dviewmatrix, "projmatrix": self.engine.dL_dprojmatrix,
+                               "camera_center": self.neural.dL_dcamera_center}
+        return loss
+
+    def pose_gradient(self, kf: Keyframe, gt: torch.Tensor) -> torch.Tensor:
+        """Forward + loss + the camera forms of both backwards for ONE keyframe against the map as it is: fills `pose_grads`
+        and returns the loss (a device scalar).  No optimizer step: parameters, Adam moments and step counts, the iteration
+        number and the densification statistics are untouched, and model.grads -- which must be zero on entry, as between
+        iterations -- is zero again on return.  What tracking against a fixed map calls (pose_refine.PoseRefiner)."""
+        if not self.pose_grad:
+            raise ValueError("pose_gradient needs a step made with pose_grad=True")
+        self._redo_if_dropped()              # (a training iteration still in flight resolves its overflow word first)
+        loss = self._forward_backward(kf, gt)
+        if self.engine.resident and not self.engine.check(raise_on_overflow=False):
+            # the resident scratch overflowed (first use of a size): the forward after the check re-calibrates
+            self.model.grads.zero_()
+            loss = self._forward_backward(kf, gt)
+        self.model.grads.zero_()
         return loss
 
     def _row_mask_of(self, gt: torch.Tensor):
@@ -731,6 +770,8 @@ class ScaffoldTrainerStep:
         resident rasterizer, a target without blanked rows) from a captured hipGraph.  Same kernels, same arguments, same
         order as the eager path: parameters stay bit-identical (tests/test_graph_step_gpu.py); what goes is the host's
         per-launch cost and the gaps between dependent small launches."""
+        if on and self.pose_grad:
+            raise ValueError("graph capture of the pose-gradient path is not supported (pose_grad=True)")
         self.use_graph = bool(on)
         self._graphs.clear()
 

@@ -8,8 +8,13 @@ pulls the pose back from close by; the defaults keep 5000 Gaussians, enlarge the
 off, from where the pose comes back to 0.01 degrees and 0.01 mm (profiles/track_pose_c1.txt).  From 0.5 degrees and 1 cm the
 starting loss is a hundred times larger and Adam walks away: that start is outside the basin of this scene.
 
+--scaffold tracks against an anchor map instead (neural_gaussians.synthetic_model): the Gaussians are then MLP outputs of the
+view direction, so the pose gradient has a third part, dL/dcamera_center of the generator.  The target is the
+map's own render at the true pose (L1/SSIM, colour only); ScaffoldTrainerStep.pose_gradient gives the three device gradients and
+pose_refine.PoseRefiner takes them to the 6-dof pose.  Same columns (the depth column is 0).
+
 usage (GPU box): python tools/track_pose.py [--workload c1] [--gaussians 5000] [--iters 200] [--rot-deg 0.2] [--shift 0.004]
-                                            [--scale-mult 6] [--lr 1e-4]"""
+                                            [--scale-mult 6] [--lr 1e-4] [--scaffold [--anchors 4000]]"""
 import argparse
 import math
 import os
@@ -37,6 +42,50 @@ def delta(xi):
     return D + corner
 
 
+def pose_errors(V_true, V):
+    E = (torch.linalg.inv(V_true.double()) @ V.double()).cpu().numpy()     # the residual camera motion, transposed layout
+    ang = math.degrees(math.acos(max(-1.0, min(1.0, (np.trace(E[:3, :3]) - 1) / 2))))
+    return ang, float(np.linalg.norm(E[3, :3]))
+
+
+def start_offset(opt):
+    axis = np.array([0.3, -0.8, 0.5]) / np.linalg.norm([0.3, -0.8, 0.5])
+    return np.concatenate([axis * math.radians(opt.rot_deg), np.array([1.0, -0.5, 0.7]) / np.linalg.norm([1.0, -0.5, 0.7]) * opt.shift])
+
+
+def main_scaffold(opt):
+    from segs_slam_amd import neural_gaussians as ng
+    from segs_slam_amd.pose_refine import PoseRefiner
+    dev = "cuda:0"
+    cam = scenes.make_config_camera(opt.workload)
+    model = ng.synthetic_model(opt.anchors, ng.ModelDims(appearance_dim=16, use_feat_bank=False), cam, dev, seed=0)
+    step = ng.ScaffoldTrainerStep(model, cam.width, cam.height, pose_grad=True)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    V_true, Pm = t(cam.world_view_transform), t(cam.projection_matrix)
+    pose7 = torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], device=dev)
+
+    def keyframe(V):
+        return ng.Keyframe(V.contiguous(), (V @ Pm).contiguous(), torch.linalg.inv(V)[3, :3].contiguous(), pose7, cam.tanfovx, cam.tanfovy)
+
+    gt = step.render(keyframe(V_true)).clone()
+    V_start = V_true @ delta(torch.tensor(start_offset(opt), dtype=torch.float32, device=dev))
+    refiner = PoseRefiner(lr=opt.lr)
+    pose = refiner.add(0, keyframe(V_start))
+    print(f"# track_pose --scaffold: {opt.workload} A={model.A} x 10 offsets {cam.width}x{cam.height}, start off by {opt.rot_deg} deg / "
+          f"{opt.shift} m, Adam lr {opt.lr}")
+    print("# iter  loss  colour_l1  depth_l1  rotation_error_deg  translation_error_m")
+    for it in range(opt.iters + 1):
+        kf = refiner.keyframe(0)
+        loss = step.pose_gradient(kf, gt)
+        l_col = (step.engine.out_color - gt).abs().mean()
+        ang, sh = pose_errors(V_true, kf.view)
+        print(f"{it:4d}  {float(loss):.6f}  {float(l_col):.6f}  {0.0:.6f}  {ang:.4f}  {sh:.5f}")
+        if it == opt.iters:
+            break
+        pose.accumulate(step.pose_grads)
+        refiner.step()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c1")
@@ -46,7 +95,11 @@ def main():
     ap.add_argument("--shift", type=float, default=0.004)
     ap.add_argument("--scale-mult", type=float, default=6.0)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--scaffold", action="store_true", help="track against an anchor map (neural Gaussians) through pose_gradient")
+    ap.add_argument("--anchors", type=int, default=4000, help="--scaffold: anchors of the synthetic map")
     opt = ap.parse_args()
+    if opt.scaffold:
+        return main_scaffold(opt)
     dev = "cuda:0"
     sc = scenes.make_config_scene(opt.workload, P=opt.gaussians)
     sc.scales *= opt.scale_mult
@@ -65,8 +118,7 @@ def main():
     with torch.no_grad():
         img_gt, _, depth_gt, _ = render(V_true)
     # the starting pose: the true one moved by a fixed rotation and shift; the optimised xi acts on top of it
-    axis = np.array([0.3, -0.8, 0.5]) / np.linalg.norm([0.3, -0.8, 0.5])
-    off = np.concatenate([axis * math.radians(opt.rot_deg), np.array([1.0, -0.5, 0.7]) / np.linalg.norm([1.0, -0.5, 0.7]) * opt.shift])
+    off = start_offset(opt)
     V_start = V_true @ delta(torch.tensor(off, dtype=torch.float32, device=dev))
     xi = torch.zeros(6, device=dev, requires_grad=True)
     adam = torch.optim.Adam([xi], lr=opt.lr)
@@ -75,9 +127,7 @@ def main():
     print("# iter  loss  colour_l1  depth_l1  rotation_error_deg  translation_error_m")
 
     def errors(V):
-        E = (torch.linalg.inv(V_true.double()) @ V.double()).cpu().numpy()     # the residual camera motion, transposed layout
-        ang = math.degrees(math.acos(max(-1.0, min(1.0, (np.trace(E[:3, :3]) - 1) / 2))))
-        return ang, float(np.linalg.norm(E[3, :3]))
+        return pose_errors(V_true, V)
 
     for it in range(opt.iters + 1):
         V = V_start @ delta(xi)
