@@ -71,8 +71,10 @@ int segs_set_doubles(double* device_dst, const double* host_values, int n, void*
  * (src/gaussian_trainer.cpp:89-90, src/gaussian_mapper.cpp:924-928 with loss_utils::l1_loss / ssim,
  * include/loss_utils.h:29-32,51-124: 11x11 window, sigma 1.5, zero padding 5, C1 = 1e-4, C2 = 9e-4, mean over all
  * 3*H*W elements).  img1/img2/dL_dimg1 are (3,H,W) planar fp32; loss_out is 3 device floats {loss, l1, ssim};
- * temp holds segs_l1_ssim_temp_bytes(H, W) bytes. */
+ * temp holds segs_l1_ssim_temp_bytes(H, W) bytes.  segs_l1_ssim_tile_rows (host only) says which of the two kernel variants the
+ * call launches at that size: 32 x 32 output tiles (returns 32) or 32 x 16 (returns 16); 0 for a non-positive size. */
 size_t segs_l1_ssim_temp_bytes(int H, int W);
+int segs_l1_ssim_tile_rows(int H, int W);
 int segs_l1_ssim_loss(const float* img1, const float* img2, int H, int W, float lambda_dssim, float* loss_out,
                       float* dL_dimg1, char* temp, void* stream);
 

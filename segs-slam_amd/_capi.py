@@ -114,6 +114,7 @@ SYMBOLS.update({
     "segs_reproject_depths_pinhole": (_i, [_i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "segs_search_neighborhood_depth": (_i, [_i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "segs_l1_ssim_temp_bytes": (_sz, [_i, _i]),
+    "segs_l1_ssim_tile_rows": (_i, [_i, _i]),
     "segs_l1_ssim_loss": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "segs_freq_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "segs_spectrum_magnitude": (_i, [_vp, _sz, _vp, _vp]),

@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__
                                                        Win win, const float* __restrict__ Dm, const float* __restrict__ D11,
                                                        const float* __restrict__ D12, float w_l1, float w_ssim,
                                                        float* __restrict__ dL, const float2* __restrict__ partial, int n_partial,
-                                                       float inv_n, float lambda_dssim, float* __restrict__ loss_out) {
+                                                       float n_total, float lambda_dssim, float* __restrict__ loss_out) {
   constexpr int IH = TY + 2 * HALO;
   constexpr int RPT = TY / 8;
   __shared__ __attribute__((aligned(16))) float s[3][IH][SP];
@@ -248,7 +248,8 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__
     if ((tid & 63) == 0) { r1[tid >> 6] = a; r2[tid >> 6] = b; }
     __syncthreads();
     if (tid == 0) {
-      const float l1 = ((r1[0] + r1[1]) + (r1[2] + r1[3])) * inv_n, ssim = ((r2[0] + r2[1]) + (r2[2] + r2[3])) * inv_n;
+      // divided, not multiplied by a rounded 1 / N: N ones must give a mean of exactly 1 (N * fl(1 / N) is 1 - 2^-24 at 11 x 10)
+      const float l1 = ((r1[0] + r1[1]) + (r1[2] + r1[3])) / n_total, ssim = ((r2[0] + r2[1]) + (r2[2] + r2[3])) / n_total;
       loss_out[0] = (1.f - lambda_dssim) * l1 + lambda_dssim * (1.f - ssim);
       loss_out[1] = l1;
       loss_out[2] = ssim;
@@ -268,6 +269,7 @@ static size_t partial_bytes(int H, int W) {
   return (nblk * sizeof(float2) + 255) & ~(size_t)255;
 }
 size_t segs_l1_ssim_temp_bytes(int H, int W) { return (size_t)3 * 3 * H * W * sizeof(float) + partial_bytes(H, W); }
+int segs_l1_ssim_tile_rows(int H, int W) { return H > 0 && W > 0 ? tile_rows(H, W) : 0; }
 
 int segs_l1_ssim_loss(const float* img1, const float* img2, int H, int W, float lambda_dssim, float* loss_out, float* dL_dimg1,
                       char* temp, void* stream) {
@@ -293,9 +295,9 @@ int segs_l1_ssim_loss(const float* img1, const float* img2, int H, int W, float 
   const float inv_n = 1.0f / (float)plane3;
   const int n_partial = (int)(grid.x * grid.y * grid.z);
   if (ty == 32) ssim_bwd_kernel<32><<<grid, block, 0, st>>>(img1, img2, H, W, win, Dm, D11, D12, (1.f - lambda_dssim) * inv_n, lambda_dssim * inv_n, dL_dimg1,
-                                                            partial, n_partial, inv_n, lambda_dssim, loss_out);
+                                                            partial, n_partial, (float)plane3, lambda_dssim, loss_out);
   else ssim_bwd_kernel<16><<<grid, block, 0, st>>>(img1, img2, H, W, win, Dm, D11, D12, (1.f - lambda_dssim) * inv_n, lambda_dssim * inv_n, dL_dimg1,
-                                                   partial, n_partial, inv_n, lambda_dssim, loss_out);
+                                                   partial, n_partial, (float)plane3, lambda_dssim, loss_out);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SEGS_OK : segs::set_hip_error(e, __func__);
 }

@@ -5,24 +5,10 @@ import numpy as np
 import pytest
 import torch
 
+from ._adam_ref import adam_reference
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def adam_reference(p, g, m, v, lr, b1, b2, eps, step, gscale):
-    """float32 restatement of LibTorch's C++ Adam step, one rounding per operation; hyper-parameters
-    are doubles and every scalar is formed in double before it is rounded into the float32 tensor arithmetic."""
-    f = np.float32
-    bc1 = 1.0 - b1 ** step
-    bc2 = 1.0 - b2 ** step
-    step_size = f(lr / bc1)
-    sqrt_bc2 = f(np.sqrt(bc2))
-    gr = g * f(gscale)
-    m = m * f(b1) + gr * f(1.0 - b1)
-    v = v * f(b2) + gr * gr * f(1.0 - b2)
-    denom = np.sqrt(v) / sqrt_bc2 + f(eps)
-    p = p - step_size * (m / denom)
-    return p.astype(f), m.astype(f), v.astype(f)
 
 
 @pytest.mark.parametrize("sizes", [(1000, 7, 64), (3, 1, 5), (4096 * 3 + 1, 1023, 2)])
