@@ -129,6 +129,32 @@ size_t segs_freq_target_floats(const segs_freq_plan* plan);
 int segs_freq_target(segs_freq_plan* plan, const float* gt, float* target_out, void* stream);
 int segs_freq_loss(segs_freq_plan* plan, const float* image, const float* target, float* dL_inout, float* freq_loss_out,
                    float* loss_inout, void* stream);
+/* ---- Depth supervision from an RGB-D frame (csrc/depth_loss.hip) ---------------------------------------------
+ * The reference reads the sensor depth only to back-project new points (src/gaussian_mapper.cpp:1673-1676); these entry points
+ * turn the rasterizer's depth map D (sum z alpha T) and opacity map A (1 - T_final) into a loss against the sensor depth Z and
+ * its two gradient maps.  All maps are (H, W) contiguous fp32.
+ *   segs_depth_target   once per keyframe image: target_out[p] = Z[p] where Z is finite, Z > min_depth and (max_depth <= 0 or
+ *                       Z < max_depth) -- the strict comparisons of the back-projection -- else 0; N, the number of valid pixels,
+ *                       follows the map as a uint32 (target_out holds segs_depth_target_floats(H, W) floats).  min_depth < 0 is
+ *                       SEGS_ERR_INVALID_ARGUMENT.
+ *   segs_depth_loss     used = valid and A >= alpha_min;  d = D (normalize == 0) or D / A (normalize == 1; needs alpha_min > 0,
+ *                       else SEGS_ERR_INVALID_ARGUMENT and nothing is launched);  n = max(N, 1), read on the device;
+ *                           L_depth = (1/n) sum_used |d - Z|      L_alpha = (1/n) sum_valid (1 - A)
+ *                           total   = lambda_depth * L_depth + lambda_alpha * L_alpha
+ *                       (the silhouette test removes pixels from the sum, not from n).  With s = sgn(d - Z) in {-1, 0, +1}:
+ *                           normalize == 0, used:  dL/dD = lambda_depth s / n
+ *                           normalize == 1, used:  dL/dD = lambda_depth s / (n A),  dL/dA = -lambda_depth s D / (n A^2)
+ *                           every valid pixel:     dL/dA -= lambda_alpha / n;       every other entry: 0.
+ *                       Both gradient maps are overwritten in full.  loss_out = {total, L_depth, L_alpha, float(used pixels)};
+ *                       *loss_inout += total if non-NULL.  temp holds segs_depth_loss_temp_bytes(H, W) bytes.  Nothing waits for
+ *                       the device; the sums are per-workgroup partials folded in a fixed order by a second, one-workgroup launch
+ *                       (no float atomics): the same inputs give the same bits on every run. */
+typedef struct { float lambda_depth, lambda_alpha, alpha_min; int normalize; } segs_depth_loss_params;
+size_t segs_depth_target_floats(int H, int W);
+int segs_depth_target(const float* sensor_depth, int H, int W, float min_depth, float max_depth, float* target_out, void* stream);
+size_t segs_depth_loss_temp_bytes(int H, int W);
+int segs_depth_loss(const float* depth, const float* alpha, const float* target, int H, int W, const segs_depth_loss_params* p,
+                    float* dL_ddepth, float* dL_dalpha, float* loss_out, float* loss_inout, char* temp, void* stream);
 #ifdef __cplusplus
 }
 #endif

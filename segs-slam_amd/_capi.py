@@ -45,6 +45,11 @@ class CameraGrads(C.Structure):
     _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("temp", C.c_void_p)]
 
 
+class DepthLossParamsC(C.Structure):
+    """segs_depth_loss_params (include/segs_train.h)."""
+    _fields_ = [("lambda_depth", C.c_float), ("lambda_alpha", C.c_float), ("alpha_min", C.c_float), ("normalize", C.c_int)]
+
+
 class AdamSegment(C.Structure):
     """segs_adam_segment (include/segs_train.h)."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_double)]
@@ -127,6 +132,10 @@ SYMBOLS.update({
     "segs_freq_target_floats": (_sz, [_vp]),
     "segs_freq_target": (_i, [_vp, _vp, _vp, _vp]),
     "segs_freq_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "segs_depth_target_floats": (_sz, [_i, _i]),
+    "segs_depth_target": (_i, [_vp, _i, _i, _f, _f, _vp, _vp]),
+    "segs_depth_loss_temp_bytes": (_sz, [_i, _i]),
+    "segs_depth_loss": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "segs_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_int64, _f, _i, _vp]),
     "segs_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_int64, _f, _i, _vp, _vp]),
     "segs_adam_step_device": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _vp, _i, _f, _i, _vp, _vp]),

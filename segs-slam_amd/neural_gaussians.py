@@ -350,7 +350,8 @@ class ScaffoldTrainerStep:
     all on the device without a host synchronisation in steady state."""
 
     def __init__(self, model: ScaffoldModel, width: int, height: int, opt: Optional[ScaffoldOptimizationParams] = None,
-                 spatial_lr_scale: float = 1.0, process_group=None, scaling_reg_weight: float = 0.0, pose_grad: bool = False):
+                 spatial_lr_scale: float = 1.0, process_group=None, scaling_reg_weight: float = 0.0, pose_grad: bool = False,
+                 depth_loss=None):
         # scaling_reg_weight = 0.01 gives the mapper's loss (src/gaussian_mapper.cpp:926-928), 0 the trainer's (:89-90 of
         # src/gaussian_trainer.cpp); the mapper's FFT regularisers (:930-945): enable_frequency_regularization()
         self.scaling_reg_weight = float(scaling_reg_weight)
@@ -365,12 +366,20 @@ class ScaffoldTrainerStep:
         # part in the gradient exchange.
         self.pose_grad = bool(pose_grad)
         self.pose_grads = None
+        # depth_loss (depth_loss.DepthLossParams): the engines also render depth and opacity, and an iteration that is handed a
+        # sensor depth adds the depth term to its loss and feeds the two gradient maps to the raster backward.
+        # One FusedDepthLoss per pyramid level, like the engines; `depth_terms` = {total, L_depth, L_alpha, used pixels} of the
+        # last iteration (a view of device words; None after a colour-only one).
+        self.depth_loss = depth_loss
+        self._depth_fns = {}
+        self.depth_terms = None
         self.engine = self._make_engine(self.neural.P_capacity, width, height)
         self.loss_fn = FusedL1SSIM(height, width, dev, self.opt.lambda_dssim)
         # Gaussian-pyramid training (src/gaussian_mapper.cpp:837-858, 872-875, 913-915): a keyframe is trained at the size of
         # its current pyramid level, i.e. of the target image it hands over.  One rasterizer engine + loss object per size,
         # made on first use; `engine` / `loss_fn` / `W` / `H` always name the level of the iteration in flight.
         self._levels = {(self.W, self.H): (self.engine, self.loss_fn)}
+        self._depth_fn()
         self.bg = torch.zeros(3, dtype=torch.float32, device=dev)      # Model.white_background: set_background(True)
         self.visible_radii = torch.zeros(model.capacity, dtype=torch.int32, device=dev)
         self.spatial_lr_scale = float(spatial_lr_scale)
@@ -416,7 +425,27 @@ class ScaffoldTrainerStep:
 
     def _make_engine(self, P: int, width: int, height: int) -> RasterEngine:
         return RasterEngine(P, width, height, self.model.device, resident=True, skip_nonpositive_opacity=True,
-                            camera_grad=self.pose_grad)
+                            camera_grad=self.pose_grad, render_depth=self.depth_loss is not None)
+
+    def _depth_fn(self):
+        """The depth loss of the level in flight (None on a step without depth supervision)."""
+        if self.depth_loss is None:
+            return None
+        fn = self._depth_fns.get((self.W, self.H))
+        if fn is None:
+            from .depth_loss import FusedDepthLoss
+            fn = self._depth_fns[(self.W, self.H)] = FusedDepthLoss(self.H, self.W, self.model.device, self.depth_loss)
+        return fn
+
+    def _check_depth(self, gt: torch.Tensor, depth):
+        """A sensor depth must come to a step made with depth_loss and have its target image's size (raises before any launch)."""
+        if depth is None:
+            return
+        from .depth_loss import depth_shape
+        if self.depth_loss is None:
+            raise ValueError("a sensor depth needs a step made with depth_loss=DepthLossParams(...)")
+        if depth_shape(depth) != tuple(gt.shape[-2:]):
+            raise ValueError(f"sensor depth is {depth_shape(depth)}, its target image {tuple(gt.shape[-2:])}")
 
     def set_background(self, white: bool):
         """bg_color of GaussianMapper's constructor (src/gaussian_mapper.cpp:61-67)."""
@@ -548,6 +577,7 @@ class ScaffoldTrainerStep:
         self._levels[(self.W, self.H)] = (self.engine, self.loss_fn)     # (a caller may have wrapped the current level's loss)
         self.engine, self.loss_fn = lv
         self.W, self.H = key
+        self._depth_fn()
 
     def render(self, kf: Keyframe) -> torch.Tensor:
         ng = self.neural
@@ -568,10 +598,12 @@ class ScaffoldTrainerStep:
         return self.engine.forward(self.bg, ng.means3D, ng.colors, ng.opacity, ng.scales, ng.rotations, kf.view, kf.proj,
                                    kf.campos, kf.tanfovx, kf.tanfovy)
 
-    def _forward_backward(self, kf: Keyframe, gt: torch.Tensor, exchange=None, flag_on_host: bool = False):
+    def _forward_backward(self, kf: Keyframe, gt: torch.Tensor, exchange=None, flag_on_host: bool = False, depth=None):
         """`flag_on_host`: the caller reads the summed overflow word on the host before the gradient exchange (adjust_anchor
-        iterations), so it needs its own collective instead of riding with the gradients."""
+        iterations), so it needs its own collective instead of riding with the gradients.  `depth`: the keyframe's sensor depth
+        (tensor or depth_loss.DepthTarget) on a step made with depth_loss; None = a colour-only iteration."""
         self.use_level(gt.shape[-1], gt.shape[-2])
+        self.depth_terms = None
         if self.model.A == 0:
             # every anchor was pruned: the reference's rasterizer short-circuits P == 0 to a zero image
             # (src/rasterize_points.cu:81) and nothing receives a gradient
@@ -602,7 +634,14 @@ class ScaffoldTrainerStep:
                     loss = loss + floss
         if mask is not None:
             dL = dL * mask
-        g = self.engine.backward(dL)
+        if depth is not None:
+            # after the colour loss and the regulariser, into the same loss word; the row mask is a colour-only matter
+            dfn = self._depth_fn()
+            _, dL_ddepth, dL_dalpha = dfn(self.engine.out_depth, self.engine.out_alpha, depth, loss.view(1))
+            self.depth_terms = dfn.out
+            g = self.engine.backward(dL, dL_ddepth, dL_dalpha)
+        else:
+            g = self.engine.backward(dL)            # the call of a step without depth supervision, as it was
         self.neural.backward(g["means3D"], g["colors"], g["opacity"], g["scales"], g["rotations"], self.scaling_reg_weight,
                              camera_grad=self.pose_grad)
         if self.pose_grad:
@@ -611,19 +650,21 @@ class ScaffoldTrainerStep:
                                "camera_center": self.neural.dL_dcamera_center}
         return loss
 
-    def pose_gradient(self, kf: Keyframe, gt: torch.Tensor) -> torch.Tensor:
+    def pose_gradient(self, kf: Keyframe, gt: torch.Tensor, gt_depth=None) -> torch.Tensor:
         """Forward + loss + the camera forms of both backwards for ONE keyframe against the map as it is: fills `pose_grads`
         and returns the loss (a device scalar).  No optimizer step: parameters, Adam moments and step counts, the iteration
         number and the densification statistics are untouched, and model.grads -- which must be zero on entry, as between
-        iterations -- is zero again on return.  What tracking against a fixed map calls (pose_refine.PoseRefiner)."""
+        iterations -- is zero again on return.  What tracking against a fixed map calls (pose_refine.PoseRefiner).  `gt_depth`
+        (step made with depth_loss): the frame's sensor depth; its term joins the loss and all three pose gradients."""
         if not self.pose_grad:
             raise ValueError("pose_gradient needs a step made with pose_grad=True")
+        self._check_depth(gt, gt_depth)
         self._redo_if_dropped()              # (a training iteration still in flight resolves its overflow word first)
-        loss = self._forward_backward(kf, gt)
+        loss = self._forward_backward(kf, gt, depth=gt_depth)
         if self.engine.resident and not self.engine.check(raise_on_overflow=False):
             # the resident scratch overflowed (first use of a size): the forward after the check re-calibrates
             self.model.grads.zero_()
-            loss = self._forward_backward(kf, gt)
+            loss = self._forward_backward(kf, gt, depth=gt_depth)
         self.model.grads.zero_()
         return loss
 
@@ -643,8 +684,11 @@ class ScaffoldTrainerStep:
     def keyframe_for(self, step: int, n_keyframes: int) -> int:
         return (step * self.world + self.rank) % n_keyframes
 
-    def training_once(self, keyframes: List[Keyframe], gt_images: List[torch.Tensor]) -> torch.Tensor:
-        """One mapper iteration.  Nothing in it waits for the device except the densification iterations (adjust_anchor
+    def training_once(self, keyframes: List[Keyframe], gt_images: List[torch.Tensor], gt_depths=None) -> torch.Tensor:
+        """One mapper iteration.  `gt_depths` (step made with depth_loss): one sensor depth per keyframe -- a tensor, a prepared
+        depth_loss.DepthTarget, or None for a colour-only iteration on that keyframe.
+
+        Nothing in it waits for the device except the densification iterations (adjust_anchor
         sizes tensors on the host): a pass whose instance count outgrew the rasterizer's resident capacity on ANY rank is
         dropped on the device by every rank -- statistics and optimizer are guarded by the all-reduced overflow word, the Adam
         step counts live on the device and do not advance -- and the rank that overflowed re-sizes its scratch at its next
@@ -662,6 +706,9 @@ class ScaffoldTrainerStep:
 
         CONTRACT: the keyframe's and the target's tensors handed to a call must stay unchanged until the next call (or
         finish()) has returned -- a redo trains on them again (refresh staging buffers only after that)."""
+        if gt_depths is not None:
+            for g_, d_ in zip(gt_images, gt_depths):
+                self._check_depth(g_, d_)
         self._redo_if_dropped()
         self.iteration += 1
         if self.keyframe_selector is not None:
@@ -669,8 +716,9 @@ class ScaffoldTrainerStep:
             k = self.keyframe_selector.use_for_ranks(self.world)[self.rank]
         else:
             k = self.keyframe_for(self.iteration - 1, len(keyframes))
-        self._last_iteration = (keyframes[k], gt_images[k], self.iteration)
-        return self._iteration_body(keyframes[k], gt_images[k], self.iteration)
+        depth = None if gt_depths is None else gt_depths[k]
+        self._last_iteration = (keyframes[k], gt_images[k], self.iteration, depth)
+        return self._iteration_body(keyframes[k], gt_images[k], self.iteration, depth)
 
     def _redo_if_dropped(self):
         prev = self._last_iteration
@@ -701,7 +749,7 @@ class ScaffoldTrainerStep:
         """Iterations the device dropped and nobody ran again (0 with redo_dropped_steps after finish(); synchronises)."""
         return self.dropped_steps() - self.redone_steps
 
-    def _iteration_body(self, kf: Keyframe, gt: torch.Tensor, it: int) -> torch.Tensor:
+    def _iteration_body(self, kf: Keyframe, gt: torch.Tensor, it: int, depth=None) -> torch.Tensor:
         """Iteration `it` on keyframe `kf` (training_once; also the re-run of an iteration the device dropped)."""
         lrs = self.learning_rates(it)
         ex = self._exchange()
@@ -712,7 +760,7 @@ class ScaffoldTrainerStep:
             loss = self._training_once_graph(kf, gt, lrs, in_stat_window)
             if loss is not None:
                 return loss
-        loss = self._forward_backward(kf, gt, ex, flag_on_host=adjust_now)
+        loss = self._forward_backward(kf, gt, ex, flag_on_host=adjust_now, depth=depth)
         flag = ex.wait_flag()
         if adjust_now:
             # adjust_anchor reads tensor sizes on the host and must see a valid pass on every rank: resolve the summed
@@ -722,7 +770,7 @@ class ScaffoldTrainerStep:
                     break
                 self.engine.check(raise_on_overflow=False)     # the rank that overflowed re-calibrates in its next forward
                 self.model.grads.zero_()
-                loss = self._forward_backward(kf, gt, ex, flag_on_host=True)
+                loss = self._forward_backward(kf, gt, ex, flag_on_host=True, depth=depth)
                 flag = ex.wait_flag()
             else:
                 raise RuntimeError("resident rasterizer kept overflowing its re-sized scratch")
@@ -772,6 +820,8 @@ class ScaffoldTrainerStep:
         per-launch cost and the gaps between dependent small launches."""
         if on and self.pose_grad:
             raise ValueError("graph capture of the pose-gradient path is not supported (pose_grad=True)")
+        if on and self.depth_loss is not None:
+            raise ValueError("graph capture of the depth-supervised path is not supported (depth_loss)")
         self.use_graph = bool(on)
         self._graphs.clear()
 

@@ -10,11 +10,14 @@ starting loss is a hundred times larger and Adam walks away: that start is outsi
 
 --scaffold tracks against an anchor map instead (neural_gaussians.synthetic_model): the Gaussians are then MLP outputs of the
 view direction, so the pose gradient has a third part, dL/dcamera_center of the generator.  The target is the
-map's own render at the true pose (L1/SSIM, colour only); ScaffoldTrainerStep.pose_gradient gives the three device gradients and
-pose_refine.PoseRefiner takes them to the 6-dof pose.  Same columns (the depth column is 0).
+map's own render at the true pose: its image (L1/SSIM) and its depth map as the sensor depth (the fused depth loss of DESIGN.md
+3g, weight --lambda-depth; --silhouette counts only pixels the current render covers to 0.99).  ScaffoldTrainerStep.pose_gradient
+gives the three device gradients and pose_refine.PoseRefiner takes them to the 6-dof pose.  Same columns; the depth column is
+L_depth of the step's depth_terms.
 
 usage (GPU box): python tools/track_pose.py [--workload c1] [--gaussians 5000] [--iters 200] [--rot-deg 0.2] [--shift 0.004]
-                                            [--scale-mult 6] [--lr 1e-4] [--scaffold [--anchors 4000]]"""
+                                            [--scale-mult 6] [--lr 1e-4]
+                                            [--scaffold [--anchors 4000] [--lambda-depth 1.0] [--silhouette]]"""
 import argparse
 import math
 import os
@@ -55,11 +58,13 @@ def start_offset(opt):
 
 def main_scaffold(opt):
     from segs_slam_amd import neural_gaussians as ng
+    from segs_slam_amd.depth_loss import DepthLossParams
     from segs_slam_amd.pose_refine import PoseRefiner
     dev = "cuda:0"
     cam = scenes.make_config_camera(opt.workload)
     model = ng.synthetic_model(opt.anchors, ng.ModelDims(appearance_dim=16, use_feat_bank=False), cam, dev, seed=0)
-    step = ng.ScaffoldTrainerStep(model, cam.width, cam.height, pose_grad=True)
+    depth_loss = DepthLossParams(opt.lambda_depth, alpha_min=0.99 if opt.silhouette else 0.0)
+    step = ng.ScaffoldTrainerStep(model, cam.width, cam.height, pose_grad=True, depth_loss=depth_loss)
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
     V_true, Pm = t(cam.world_view_transform), t(cam.projection_matrix)
     pose7 = torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], device=dev)
@@ -68,18 +73,19 @@ def main_scaffold(opt):
         return ng.Keyframe(V.contiguous(), (V @ Pm).contiguous(), torch.linalg.inv(V)[3, :3].contiguous(), pose7, cam.tanfovx, cam.tanfovy)
 
     gt = step.render(keyframe(V_true)).clone()
+    gt_depth = step._depth_fn().prepare(step.engine.out_depth)       # pixels no Gaussian reaches (depth 0) are invalid
     V_start = V_true @ delta(torch.tensor(start_offset(opt), dtype=torch.float32, device=dev))
     refiner = PoseRefiner(lr=opt.lr)
     pose = refiner.add(0, keyframe(V_start))
     print(f"# track_pose --scaffold: {opt.workload} A={model.A} x 10 offsets {cam.width}x{cam.height}, start off by {opt.rot_deg} deg / "
-          f"{opt.shift} m, Adam lr {opt.lr}")
+          f"{opt.shift} m, Adam lr {opt.lr}, lambda_depth {opt.lambda_depth}{', silhouette 0.99' if opt.silhouette else ''}")
     print("# iter  loss  colour_l1  depth_l1  rotation_error_deg  translation_error_m")
     for it in range(opt.iters + 1):
         kf = refiner.keyframe(0)
-        loss = step.pose_gradient(kf, gt)
+        loss = step.pose_gradient(kf, gt, gt_depth)
         l_col = (step.engine.out_color - gt).abs().mean()
         ang, sh = pose_errors(V_true, kf.view)
-        print(f"{it:4d}  {float(loss):.6f}  {float(l_col):.6f}  {0.0:.6f}  {ang:.4f}  {sh:.5f}")
+        print(f"{it:4d}  {float(loss):.6f}  {float(l_col):.6f}  {float(step.depth_terms[1]):.6f}  {ang:.4f}  {sh:.5f}")
         if it == opt.iters:
             break
         pose.accumulate(step.pose_grads)
@@ -97,6 +103,8 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--scaffold", action="store_true", help="track against an anchor map (neural Gaussians) through pose_gradient")
     ap.add_argument("--anchors", type=int, default=4000, help="--scaffold: anchors of the synthetic map")
+    ap.add_argument("--lambda-depth", type=float, default=1.0, help="--scaffold: weight of the depth term")
+    ap.add_argument("--silhouette", action="store_true", help="--scaffold: depth term only where the render's opacity is >= 0.99")
     opt = ap.parse_args()
     if opt.scaffold:
         return main_scaffold(opt)
