@@ -181,6 +181,24 @@ def lib() -> C.CDLL:
     return _lib
 
 
+class raster_flags:
+    """The rasterizer's switches are per-host-thread state of the library: set for the calls inside only, so that the
+    reference-shaped wrappers (rasterize_points.py) keep the reference's behaviour on the same thread."""
+
+    def __init__(self, flags: int, status_mirror=None, clear_mirror: bool = True):
+        self.flags, self.status_mirror, self.clear_mirror = flags, status_mirror, clear_mirror
+
+    def __enter__(self):
+        self.old = lib().segs_raster_set_flags(self.flags)
+        if self.status_mirror is not None:
+            _lib.segs_raster_set_status_mirror(self.status_mirror)
+
+    def __exit__(self, *exc):
+        _lib.segs_raster_set_flags(self.old)
+        if self.clear_mirror:
+            _lib.segs_raster_set_status_mirror(None)
+
+
 class SegsError(RuntimeError):
     pass
 

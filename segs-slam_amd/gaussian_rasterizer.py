@@ -33,38 +33,58 @@ class GaussianRasterizationSettings:
     prefiltered_: bool = False
 
 
+def _raster_forward(ctx, fn, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
+                    sh_degree, rs):
+    """The forward of the three Functions: calls rp.`fn`, keeps on ctx what _raster_backward needs
+    -> fn's outputs without num_rendered and the three buffers: (color, radii[, depth, alpha])."""
+    num_rendered, *outputs, geomBuffer, binningBuffer, imgBuffer = fn(
+        rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3Ds_precomp, viewmatrix, projmatrix,
+        rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, sh, sh_degree, rs.campos_, rs.prefiltered_)
+    radii = outputs[1]
+    ctx.num_rendered = num_rendered
+    ctx.scale_modifier = rs.scale_modifier_
+    ctx.tanfovx, ctx.tanfovy = rs.tanfovx_, rs.tanfovy_
+    ctx.sh_degree = sh_degree
+    ctx.save_for_backward(rs.bg_, viewmatrix, projmatrix, rs.campos_, colors_precomp, means3D, scales, rotations, cov3Ds_precomp,
+                          radii, sh, geomBuffer, binningBuffer, imgBuffer)
+    ctx.mark_non_differentiable(radii)
+    return tuple(outputs)
+
+
+def _raster_backward(ctx, fn, grad_out_color, *grad_maps):
+    """Calls rp.`fn` on what _raster_forward kept -> (gradients of means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+    cov3Ds_precomp: the order of src/gaussian_rasterizer.cpp:143-153, "absent" inputs (0-element tensors) get None; fn's tuple),
+    or None when no gradient arrived at all (the map forms, which leave an unused output's gradient None)."""
+    (bg, viewmatrix, projmatrix, campos, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
+     geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
+    if grad_maps:      # a None map gradient goes down as NULL: no work for it
+        ref = next((t for t in (grad_out_color, *grad_maps) if t is not None), None)
+        if ref is None:
+            return None
+        if grad_out_color is None:      # only a map gradient arrived: a zero colour gradient stands in
+            grad_out_color = torch.zeros((3,) + tuple(ref.shape), dtype=torch.float32, device=means3D.device)
+        grad_out_color, *grad_maps = (t.contiguous() if t is not None else None for t in (grad_out_color, *grad_maps))
+    out = fn(bg, means3D, radii, colors_precomp, scales, rotations, ctx.scale_modifier, cov3Ds_precomp, viewmatrix, projmatrix,
+             ctx.tanfovx, ctx.tanfovy, grad_out_color, *grad_maps, sh, ctx.sh_degree, campos, geomBuffer, ctx.num_rendered,
+             binningBuffer, imgBuffer)
+    dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations = out[:8]
+    g = lambda t, ref: t if ref.numel() != 0 else None  # noqa: E731
+    return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity, g(dL_dscales, scales),
+            g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp)), out
+
+
 class GaussianRasterizerFunction(torch.autograd.Function):
     """src/gaussian_rasterizer.cpp:27-154."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
         rs = raster_settings
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansCUDA(
-            rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3Ds_precomp,
-            rs.viewmatrix_, rs.projmatrix_, rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, sh,
-            rs.sh_degree_, rs.campos_, rs.prefiltered_)
-        ctx.num_rendered = num_rendered
-        ctx.scale_modifier = rs.scale_modifier_
-        ctx.tanfovx, ctx.tanfovy = rs.tanfovx_, rs.tanfovy_
-        ctx.sh_degree = rs.sh_degree_
-        ctx.save_for_backward(rs.bg_, rs.viewmatrix_, rs.projmatrix_, rs.campos_, colors_precomp, means3D, scales,
-                              rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
-        return color, radii
+        return _raster_forward(ctx, rp.RasterizeGaussiansCUDA, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                        rs.viewmatrix_, rs.projmatrix_, rs.sh_degree_, rs)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii=None):
-        (bg, viewmatrix, projmatrix, campos, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-         geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
-        (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-         dL_drotations) = rp.RasterizeGaussiansBackwardCUDA(
-            bg, means3D, radii, colors_precomp, scales, rotations, ctx.scale_modifier, cov3Ds_precomp, viewmatrix,
-            projmatrix, ctx.tanfovx, ctx.tanfovy, grad_out_color, sh, ctx.sh_degree, campos, geomBuffer,
-            ctx.num_rendered, binningBuffer, imgBuffer)
-        # gradient order of src/gaussian_rasterizer.cpp:143-153; "absent" inputs (0-element tensors) get None
-        g = lambda t, ref: t if ref.numel() != 0 else None  # noqa: E731
-        return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
-                g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
+        return _raster_backward(ctx, rp.RasterizeGaussiansBackwardCUDA, grad_out_color)[0] + (None,)
 
 
 class GaussianRasterizerDepthFunction(torch.autograd.Function):
@@ -73,39 +93,14 @@ class GaussianRasterizerDepthFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
         rs = raster_settings
-        num_rendered, color, radii, depth, alpha, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansDepthCUDA(
-            rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3Ds_precomp,
-            rs.viewmatrix_, rs.projmatrix_, rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, sh,
-            rs.sh_degree_, rs.campos_, rs.prefiltered_)
-        ctx.num_rendered = num_rendered
-        ctx.scale_modifier = rs.scale_modifier_
-        ctx.tanfovx, ctx.tanfovy = rs.tanfovx_, rs.tanfovy_
-        ctx.sh_degree = rs.sh_degree_
-        ctx.save_for_backward(rs.bg_, rs.viewmatrix_, rs.projmatrix_, rs.campos_, colors_precomp, means3D, scales,
-                              rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)   # an unused map's gradient stays None and is passed down as NULL (no work for it)
-        return color, radii, depth, alpha
+        ctx.set_materialize_grads(False)
+        return _raster_forward(ctx, rp.RasterizeGaussiansDepthCUDA, means3D, sh, colors_precomp, opacities, scales, rotations,
+                        cov3Ds_precomp, rs.viewmatrix_, rs.projmatrix_, rs.sh_degree_, rs)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii=None, grad_depth=None, grad_alpha=None):
-        (bg, viewmatrix, projmatrix, campos, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-         geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 9
-        if grad_out_color is None:
-            ref = grad_depth if grad_depth is not None else grad_alpha
-            grad_out_color = torch.zeros((3,) + tuple(ref.shape), dtype=torch.float32, device=means3D.device)
-        (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-         dL_drotations) = rp.RasterizeGaussiansDepthBackwardCUDA(
-            bg, means3D, radii, colors_precomp, scales, rotations, ctx.scale_modifier, cov3Ds_precomp, viewmatrix,
-            projmatrix, ctx.tanfovx, ctx.tanfovy, grad_out_color.contiguous(),
-            grad_depth.contiguous() if grad_depth is not None else None,
-            grad_alpha.contiguous() if grad_alpha is not None else None, sh, ctx.sh_degree, campos, geomBuffer,
-            ctx.num_rendered, binningBuffer, imgBuffer)
-        g = lambda t, ref: t if ref.numel() != 0 else None  # noqa: E731
-        return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
-                g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
+        g = _raster_backward(ctx, rp.RasterizeGaussiansDepthBackwardCUDA, grad_out_color, grad_depth, grad_alpha)
+        return g[0] + (None,) if g else (None,) * 9
 
 
 class GaussianRasterizerCameraFunction(torch.autograd.Function):
@@ -116,40 +111,20 @@ class GaussianRasterizerCameraFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
                 raster_settings):
-        rs = raster_settings
-        e = torch.empty(0, dtype=torch.float32, device=means3D.device)
-        num_rendered, color, radii, depth, alpha, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansDepthCUDA(
-            rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3Ds_precomp,
-            viewmatrix, projmatrix, rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, e, 0, rs.campos_, rs.prefiltered_)
-        ctx.num_rendered = num_rendered
-        ctx.scale_modifier = rs.scale_modifier_
-        ctx.tanfovx, ctx.tanfovy = rs.tanfovx_, rs.tanfovy_
-        ctx.save_for_backward(rs.bg_, viewmatrix, projmatrix, rs.campos_, colors_precomp, means3D, scales, rotations,
-                              cov3Ds_precomp, radii, geomBuffer, binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
+        no_sh = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        return _raster_forward(ctx, rp.RasterizeGaussiansDepthCUDA, means3D, no_sh, colors_precomp, opacities, scales, rotations,
+                        cov3Ds_precomp, viewmatrix, projmatrix, 0, raster_settings)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii=None, grad_depth=None, grad_alpha=None):
-        (bg, viewmatrix, projmatrix, campos, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii,
-         geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+        g = _raster_backward(ctx, rp.RasterizeGaussiansCameraBackwardCUDA, grad_out_color, grad_depth, grad_alpha)
+        if g is None:
             return (None,) * 10
-        if grad_out_color is None:
-            ref = grad_depth if grad_depth is not None else grad_alpha
-            grad_out_color = torch.zeros((3,) + tuple(ref.shape), dtype=torch.float32, device=means3D.device)
-        e = torch.empty(0, dtype=torch.float32, device=means3D.device)
-        (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, _dL_dsh, dL_dscales, dL_drotations, dL_dview,
-         dL_dproj) = rp.RasterizeGaussiansCameraBackwardCUDA(
-            bg, means3D, radii, colors_precomp, scales, rotations, ctx.scale_modifier, cov3Ds_precomp, viewmatrix,
-            projmatrix, ctx.tanfovx, ctx.tanfovy, grad_out_color.contiguous(),
-            grad_depth.contiguous() if grad_depth is not None else None,
-            grad_alpha.contiguous() if grad_alpha is not None else None, e, 0, campos, geomBuffer,
-            ctx.num_rendered, binningBuffer, imgBuffer)
-        g = lambda t, ref: t if ref.numel() != 0 else None  # noqa: E731
-        return (dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, g(dL_dscales, scales), g(dL_drotations, rotations),
-                g(dL_dcov3D, cov3Ds_precomp), dL_dview.to(viewmatrix.dtype), dL_dproj.to(projmatrix.dtype), None)
+        (dL_dmeans3D, dL_dmeans2D, _, _, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D), out = g
+        viewmatrix, projmatrix = ctx.saved_tensors[1:3]
+        return (dL_dmeans3D, dL_dmeans2D, out[1], dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, out[8].to(viewmatrix.dtype),
+                out[9].to(projmatrix.dtype), None)      # out[1]: dL_dcolors as the wrapper returns it, never "absent" here
 
 
 def rasterizeGaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
@@ -180,8 +155,11 @@ class GaussianRasterizer(torch.nn.Module):
         super().__init__()
         self.raster_settings_ = raster_settings
 
-    def _absent(self, like: torch.Tensor) -> torch.Tensor:
-        return torch.empty(0, dtype=torch.float32, device=like.device)
+    @staticmethod
+    def _or_absent(like: torch.Tensor, has, tensors):
+        """-> each of `tensors`, or where its `has` is false the reference's "absent": a 0-element tensor on like's device."""
+        e = torch.empty(0, dtype=torch.float32, device=like.device)
+        return [t if h else e for h, t in zip(has, tensors)]
 
     def markVisibleGaussians(self, positions):
         with torch.no_grad():
@@ -198,12 +176,9 @@ class GaussianRasterizer(torch.nn.Module):
     def forward(self, means3D, means2D, opacities, has_shs, has_colors_precomp, has_scales, has_rotations,
                 has_cov3D_precomp, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
         self._check(has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp)
-        e = self._absent(means3D)
-        shs = shs if has_shs else e
-        colors_precomp = colors_precomp if has_colors_precomp else e
-        scales = scales if has_scales else e
-        rotations = rotations if has_rotations else e
-        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        shs, colors_precomp, scales, rotations, cov3D_precomp = self._or_absent(
+            means3D, (has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp),
+            (shs, colors_precomp, scales, rotations, cov3D_precomp))
         color, radii = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                           cov3D_precomp, self.raster_settings_)
         return color, radii
@@ -212,12 +187,9 @@ class GaussianRasterizer(torch.nn.Module):
                            has_cov3D_precomp, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
         """forward() plus the depth map (sum z alpha T) and alpha map (1 - T_final): -> (color, radii, depth, alpha)."""
         self._check(has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp)
-        e = self._absent(means3D)
-        shs = shs if has_shs else e
-        colors_precomp = colors_precomp if has_colors_precomp else e
-        scales = scales if has_scales else e
-        rotations = rotations if has_rotations else e
-        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        shs, colors_precomp, scales, rotations, cov3D_precomp = self._or_absent(
+            means3D, (has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp),
+            (shs, colors_precomp, scales, rotations, cov3D_precomp))
         return rasterizeGaussiansWithDepth(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                            self.raster_settings_)
 
@@ -227,10 +199,8 @@ class GaussianRasterizer(torch.nn.Module):
         tensors) are inputs of the autograd graph.  Precomputed colours only.  -> (color, radii, depth, alpha)."""
         self._check(False, True, has_scales, has_rotations, has_cov3D_precomp)
         rs = self.raster_settings_
-        e = self._absent(means3D)
-        scales = scales if has_scales else e
-        rotations = rotations if has_rotations else e
-        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        scales, rotations, cov3D_precomp = self._or_absent(means3D, (has_scales, has_rotations, has_cov3D_precomp),
+                                                           (scales, rotations, cov3D_precomp))
         return rasterizeGaussiansWithCameraGrad(means3D, means2D, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                                 rs.viewmatrix_ if viewmatrix is None else viewmatrix,
                                                 rs.projmatrix_ if projmatrix is None else projmatrix, rs)
@@ -238,10 +208,8 @@ class GaussianRasterizer(torch.nn.Module):
     def visible_filter(self, means3D, has_scales, has_rotations, has_cov3D_precomp, scales=None, rotations=None,
                        cov3D_precomp=None):
         rs = self.raster_settings_
-        e = self._absent(means3D)
-        scales = scales if has_scales else e
-        rotations = rotations if has_rotations else e
-        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        scales, rotations, cov3D_precomp = self._or_absent(means3D, (has_scales, has_rotations, has_cov3D_precomp),
+                                                           (scales, rotations, cov3D_precomp))
         with torch.no_grad():
             return rp.RasterizeGaussiansfilterCUDA(means3D, scales, rotations, rs.scale_modifier_, cov3D_precomp,
                                                    rs.viewmatrix_, rs.projmatrix_, rs.tanfovx_, rs.tanfovy_,
@@ -251,12 +219,9 @@ class GaussianRasterizer(torch.nn.Module):
                        has_cov3D_precomp, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
         self._check(has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp)
         rs = self.raster_settings_
-        e = self._absent(means3D)
-        shs = shs if has_shs else e
-        colors_precomp = colors_precomp if has_colors_precomp else e
-        scales = scales if has_scales else e
-        rotations = rotations if has_rotations else e
-        cov3D_precomp = cov3D_precomp if has_cov3D_precomp else e
+        shs, colors_precomp, scales, rotations, cov3D_precomp = self._or_absent(
+            means3D, (has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp),
+            (shs, colors_precomp, scales, rotations, cov3D_precomp))
         points_image_2d, radii, color = rp.RasterizeGaussiansprojectCUDA(
             rs.bg_, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier_, cov3D_precomp,
             rs.viewmatrix_, rs.projmatrix_, rs.tanfovx_, rs.tanfovy_, rs.image_height_, rs.image_width_, shs,

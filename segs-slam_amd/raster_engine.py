@@ -34,6 +34,10 @@ class _GrowBuffer:
         return _capi.ALLOC_FN(_alloc)
 
 
+def _p(t: torch.Tensor) -> C.c_void_p:
+    return C.c_void_p(t.data_ptr())
+
+
 def split_flat(flat: torch.Tensor, P: int):
     """Views (P,n) into a flat FLOATS_PER_GAUSSIAN*P buffer, field-major (each field contiguous)."""
     out, off = {}, 0
@@ -83,7 +87,8 @@ class RasterEngine:
         self.out_color = torch.zeros((3, self.H, self.W), **f)
         self.out_depth = torch.zeros((self.H, self.W), **f) if self.render_depth else None
         self.out_alpha = torch.zeros((self.H, self.W), **f) if self.render_depth else None
-        self._depth_out = _capi.DepthOutputs(self.out_depth.data_ptr(), self.out_alpha.data_ptr()) if self.render_depth else None
+        self._depth_out_ref = (C.byref(_capi.DepthOutputs(self.out_depth.data_ptr(), self.out_alpha.data_ptr()))
+                               if self.render_depth else None)
         self.radii = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
         # (+4 floats behind the bucket: keyframe_parallel.BucketExchange lets the overflow word ride there in a dense exchange)
         self.grads_flat = torch.zeros((FLOATS_PER_GAUSSIAN * self.P + 4,), **f)[:FLOATS_PER_GAUSSIAN * self.P]
@@ -92,10 +97,14 @@ class RasterEngine:
         # dL/dcov3D has no consumer when the Gaussians come as scales + rotations (the training path): written on request only;
         # dL/dconic, the tile backward's internal product, is never materialised here (40 B per Gaussian less to write)
         self.dL_dcov3D = torch.zeros((self.P, 6), **f) if want_cov3D_grad else None
+        # where every backward writes, in the entry points' order; made once, these tensors are never reallocated
+        self._grad_ptrs = (_p(self.dL_dmean2D), None, *(_p(self.grads[k]) for k in ("opacity", "colors", "means3D")),
+                           _p(self.dL_dcov3D) if want_cov3D_grad else None, None, _p(self.grads["scales"]), _p(self.grads["rotations"]))
         self.geom, self.binning, self.img = (_GrowBuffer(self.device) for _ in range(3))
         self.R = 0
         self._lib = _capi.lib()
         self._last = None
+        self._last_resident = False
         self.dL_dviewmatrix = torch.zeros((4, 4), **f) if self.camera_grad else None
         self.dL_dprojmatrix = torch.zeros((4, 4), **f) if self.camera_grad else None
         self._camera_out = None
@@ -123,8 +132,10 @@ class RasterEngine:
         self._geom_r = torch.zeros(self._lib.segs_geometry_bytes(self.P), dtype=torch.uint8, device=dev)
         self._img_r = torch.empty(self._lib.segs_image_bytes(self.W, self.H), dtype=torch.uint8, device=dev)
         self._bin_r = torch.empty(self._lib.segs_resident_binning_bytes(self.P, self.capacity), dtype=torch.uint8, device=dev)
+        self._scratch_r = (_p(self._geom_r), _p(self._bin_r), _p(self._img_r))
         self._status = torch.zeros(4, dtype=torch.int32, device=dev)
         self._status_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self._status_mirror = C.c_void_p(self._status_host.data_ptr())
         self._status_event = torch.cuda.Event()
         self._status_pending = False
 
@@ -151,69 +162,58 @@ class RasterEngine:
             return self.check(raise_on_overflow=False)
         return True
 
+    def _status_issued(self, capturing: bool = False):
+        """The last binning kernel of a resident forward stores R and the overflow word into the pinned host words: mark when."""
+        if not capturing:
+            self._status_event.record(torch.cuda.current_stream(self.device))
+            self._status_pending = True
+        self._last_resident = True
+
     def after_graph_replay(self):
         """Bookkeeping of a resident forward + backward that ran from a captured graph (the Python side of forward() did not)."""
-        self._status_event.record(torch.cuda.current_stream(self.device))
-        self._status_pending = True
-        self._last_resident = True
+        self._status_issued()
+
+    def _twin(self, name: str, args: tuple):
+        """(entry point, arguments without the stream) of a forward, or of its `_depth` twin for a render_depth engine."""
+        return (name + "_depth", args + (self._depth_out_ref,)) if self.render_depth else (name, args)
+
+    def _call(self, name: str, args: tuple):
+        _capi.check(getattr(self._lib, name)(*args, self._stream()), name)
 
     def forward(self, bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
                 scale_modifier: float = 1.0) -> torch.Tensor:
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        for t in (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos):
+        last = (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier)
+        for t in last[:9]:
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
         if self.resident and self.capacity > 0:
             self.check(raise_on_overflow=False)  # an overflow noticed here was already handled by the caller's own check
-        # the two switches are per-host-thread state of the library: set for this call only, restored afterwards, so that
-        # the reference-shaped wrappers (rasterize_points.py) keep the reference's behaviour on the same thread
-        old_flags = self._lib.segs_raster_set_flags(self.flags)
-        try:
-            return self._forward(p, bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx,
-                                 tanfovy, scale_modifier)
-        finally:
-            self._lib.segs_raster_set_flags(old_flags)
-            self._lib.segs_raster_set_status_mirror(None)
-
-    def _forward(self, p, bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
-                 scale_modifier):
-        if self.resident and self.capacity > 0:
-            self._lib.segs_raster_set_status_mirror(C.c_void_p(self._status_host.data_ptr()))
-            args = (p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, 0, 0, p(bg), self.W, self.H,
-                    p(means3D), None, p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix),
-                    p(projmatrix), p(campos), float(tanfovx), float(tanfovy), p(self.out_color), p(self.radii), p(self._status))
-            if self.render_depth:
-                st = self._lib.segs_rasterize_forward_resident_depth(*args, C.byref(self._depth_out), self._stream())
-                _capi.check(st, "segs_rasterize_forward_resident_depth")
+        resident = self.resident and self.capacity > 0
+        with _capi.raster_flags(self.flags, self._status_mirror if resident else None):
+            if resident:
+                self._call(*self._twin("segs_rasterize_forward_resident", (
+                    *self._scratch_r, self.capacity, self.P, self.P_active, 0, 0, _p(bg), self.W, self.H, _p(means3D), None, _p(colors),
+                    _p(opacity), _p(scales), float(scale_modifier), _p(rotations), None, _p(viewmatrix), _p(projmatrix), _p(campos),
+                    float(tanfovx), float(tanfovy), _p(self.out_color), _p(self.radii), _p(self._status))))
+                self._status_issued(torch.cuda.is_current_stream_capturing())
             else:
-                st = self._lib.segs_rasterize_forward_resident(*args, self._stream())
-                _capi.check(st, "segs_rasterize_forward_resident")
-            if not torch.cuda.is_current_stream_capturing():
-                # R and the overflow word were stored into the pinned host words by the last binning kernel
-                self._status_event.record(torch.cuda.current_stream(self.device))
-                self._status_pending = True
-            self._last = (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
-                          scale_modifier)
-            self._last_resident = True
-            return self.out_color
-        self._last_resident = False
-        n = C.c_int(0)
-        gcb, bcb, icb = self.geom.callback(), self.binning.callback(), self.img.callback()
-        args = (gcb, None, bcb, None, icb, None, self.P_active, 0, 0, p(bg), self.W, self.H, p(means3D),
-                None, p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix),
-                p(campos), float(tanfovx), float(tanfovy), 0, p(self.out_color), p(self.radii))
-        if self.render_depth:
-            st = self._lib.segs_rasterize_forward_depth(*args, C.byref(self._depth_out), self._stream(), C.byref(n))
-            _capi.check(st, "segs_rasterize_forward_depth")
-        else:
-            st = self._lib.segs_rasterize_forward(*args, self._stream(), C.byref(n))
-            _capi.check(st, "segs_rasterize_forward")
-        self.R = int(n.value)
-        self.R_reference = self.R     # the reference's num_rendered (bounding-square duplication, rasterizer_impl.cu:70-111)
-        self._last = (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
-                      scale_modifier)
+                self._last_resident = False
+                n = C.c_int(0)
+                name, args = self._forward_args(*(b.callback() for b in (self.geom, self.binning, self.img)), n, *last)
+                _capi.check(getattr(self._lib, name)(*args[:-1], self._stream(), args[-1]), name)
+                self.R = self.R_reference = int(n.value)   # the reference's num_rendered (bounding squares, rasterizer_impl.cu:70-111)
+        self._last = last
         if self.resident and self.capacity == 0:
             self._setup_resident(self.R)  # calibrated: later forwards take the no-sync path
         return self.out_color
+
+    def _forward_args(self, gcb, bcb, icb, n, bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx,
+                      tanfovy, scale_modifier):
+        """The synchronising forward -> (entry point, its arguments without the stream, which goes before the last).  No device."""
+        name, args = self._twin("segs_rasterize_forward", (
+            gcb, None, bcb, None, icb, None, self.P_active, 0, 0, _p(bg), self.W, self.H, _p(means3D), None, _p(colors), _p(opacity),
+            _p(scales), float(scale_modifier), _p(rotations), None, _p(viewmatrix), _p(projmatrix), _p(campos), float(tanfovx),
+            float(tanfovy), 0, _p(self.out_color), _p(self.radii)))
+        return name, args + (C.byref(n),)
 
     def can_take_projected(self) -> bool:
         """The resident buffers are calibrated: a producer may run K1 itself (projection_targets / forward_projected)."""
@@ -223,14 +223,10 @@ class RasterEngine:
         """Where a producer that projects its own Gaussians leaves K1's outputs for the next forward_projected call
         (segs_resident_projection_targets); made under this engine's flags."""
         assert self.can_take_projected()
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         tg = _capi.ProjectionTargets()
-        old_flags = self._lib.segs_raster_set_flags(self.flags)
-        try:
-            st = self._lib.segs_resident_projection_targets(p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P,
-                                                            self.P_active, self.W, self.H, p(self.radii), p(self._status), C.byref(tg))
-        finally:
-            self._lib.segs_raster_set_flags(old_flags)
+        with _capi.raster_flags(self.flags, clear_mirror=False):
+            st = self._lib.segs_resident_projection_targets(*self._scratch_r, self.capacity, self.P, self.P_active, self.W, self.H,
+                                                            _p(self.radii), _p(self._status), C.byref(tg))
         _capi.check(st, "segs_resident_projection_targets")
         return tg
 
@@ -239,27 +235,33 @@ class RasterEngine:
         """The resident forward WITHOUT its per-Gaussian stage: the producer has written records, radii, tile counts and depth
         keys into projection_targets().  means3D / scales / rotations are what the backward will re-read."""
         assert self.can_take_projected()   # (the caller resolved the previous step's status before it asked for the targets)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        old_flags = self._lib.segs_raster_set_flags(self.flags)
-        try:
-            self._lib.segs_raster_set_status_mirror(C.c_void_p(self._status_host.data_ptr()))
-            args = (p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, p(bg), self.W, self.H,
-                    p(self.out_color), p(self._status))
-            if self.render_depth:
-                st = self._lib.segs_rasterize_forward_resident_projected_depth(*args, C.byref(self._depth_out), self._stream())
-                _capi.check(st, "segs_rasterize_forward_resident_projected_depth")
-            else:
-                st = self._lib.segs_rasterize_forward_resident_projected(*args, self._stream())
-                _capi.check(st, "segs_rasterize_forward_resident_projected")
-        finally:
-            self._lib.segs_raster_set_flags(old_flags)
-            self._lib.segs_raster_set_status_mirror(None)
-        if not torch.cuda.is_current_stream_capturing():
-            self._status_event.record(torch.cuda.current_stream(self.device))
-            self._status_pending = True
+        with _capi.raster_flags(self.flags, self._status_mirror):
+            self._call(*self._twin("segs_rasterize_forward_resident_projected", (
+                *self._scratch_r, self.capacity, self.P, self.P_active, _p(bg), self.W, self.H, _p(self.out_color), _p(self._status))))
+        self._status_issued(torch.cuda.is_current_stream_capturing())
         self._last = (bg, means3D, None, None, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier)
-        self._last_resident = True
         return self.out_color
+
+    def _backward_args(self, dL_dout_color, depth_grads=None, camera_out=None):
+        """The backward of the last forward -> (entry point, its arguments without the stream, which comes last): the `_camera`
+        form with a camera_out struct, the `_depth` form with depth_grads alone.  No device needed after a synchronising forward."""
+        bg, means3D, colors, _, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier = self._last
+        if self._last_resident:
+            name = "segs_rasterize_backward_resident"
+            args = (*self._scratch_r, self.capacity, self.P, self.P_active, 0, 0, _p(bg), self.W, self.H, _p(means3D), None, _p(scales),
+                    float(scale_modifier), _p(rotations), None, _p(viewmatrix), _p(projmatrix), _p(campos), float(tanfovx),
+                    float(tanfovy), _p(self.radii))
+        else:
+            name = "segs_rasterize_backward"
+            args = (self.P_active, 0, 0, self.R, _p(bg), self.W, self.H, _p(means3D), None, _p(colors), _p(scales),
+                    float(scale_modifier), _p(rotations), None, _p(viewmatrix), _p(projmatrix), _p(campos), float(tanfovx),
+                    float(tanfovy), _p(self.radii), _p(self.geom.tensor), _p(self.binning.tensor), _p(self.img.tensor))
+        args += (_p(dL_dout_color), *self._grad_ptrs)
+        if camera_out is not None:
+            return name + "_camera", args + (C.byref(depth_grads) if depth_grads is not None else None, C.byref(camera_out))
+        if depth_grads is not None:
+            return name + "_depth", args + (C.byref(depth_grads),)
+        return name, args
 
     def backward(self, dL_dout_color: torch.Tensor, dL_ddepth: torch.Tensor = None, dL_dalpha: torch.Tensor = None,
                  camera_grad: bool = None):
@@ -269,8 +271,6 @@ class RasterEngine:
         camera_out = self._camera_out if (camera_grad is None or camera_grad) else None
         if camera_grad and camera_out is None:
             raise ValueError("camera gradients need an engine made with camera_grad=True")
-        (bg, means3D, colors, opacity, scales, rotations, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
-         scale_modifier) = self._last
         assert dL_dout_color.is_contiguous() and dL_dout_color.dtype == torch.float32
         depth_grads = None
         if dL_ddepth is not None or dL_dalpha is not None:
@@ -278,43 +278,9 @@ class RasterEngine:
                 raise ValueError("depth / alpha gradients need an engine made with render_depth=True")
             for t in (dL_ddepth, dL_dalpha):
                 assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (self.H, self.W))
-            depth_grads = _capi.DepthGrads(dL_ddepth.data_ptr() if dL_ddepth is not None else None,
-                                           dL_dalpha.data_ptr() if dL_dalpha is not None else None)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        pn = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        g = self.grads
-        if getattr(self, "_last_resident", False):
-            args = (p(self._geom_r), p(self._bin_r), p(self._img_r), self.capacity, self.P, self.P_active, 0, 0, p(bg), self.W, self.H,
-                    p(means3D), None, p(scales), float(scale_modifier), p(rotations), None, p(viewmatrix), p(projmatrix), p(campos),
-                    float(tanfovx), float(tanfovy), p(self.radii), p(dL_dout_color), p(self.dL_dmean2D), None,
-                    p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]), p(g["rotations"]))
-            if camera_out is not None:
-                st = self._lib.segs_rasterize_backward_resident_camera(*args, C.byref(depth_grads) if depth_grads is not None else None,
-                                                                       C.byref(camera_out), self._stream())
-                _capi.check(st, "segs_rasterize_backward_resident_camera")
-            elif depth_grads is not None:
-                st = self._lib.segs_rasterize_backward_resident_depth(*args, C.byref(depth_grads), self._stream())
-                _capi.check(st, "segs_rasterize_backward_resident_depth")
-            else:
-                st = self._lib.segs_rasterize_backward_resident(*args, self._stream())
-                _capi.check(st, "segs_rasterize_backward_resident")
-            return g
-        args = (self.P_active, 0, 0, self.R, p(bg), self.W, self.H, p(means3D), None, p(colors), p(scales), float(scale_modifier),
-                p(rotations), None, p(viewmatrix), p(projmatrix), p(campos), float(tanfovx), float(tanfovy), p(self.radii),
-                p(self.geom.tensor), p(self.binning.tensor), p(self.img.tensor), p(dL_dout_color), p(self.dL_dmean2D),
-                None, p(g["opacity"]), p(g["colors"]), p(g["means3D"]), pn(self.dL_dcov3D), None, p(g["scales"]),
-                p(g["rotations"]))
-        if camera_out is not None:
-            st = self._lib.segs_rasterize_backward_camera(*args, C.byref(depth_grads) if depth_grads is not None else None,
-                                                          C.byref(camera_out), self._stream())
-            _capi.check(st, "segs_rasterize_backward_camera")
-        elif depth_grads is not None:
-            st = self._lib.segs_rasterize_backward_depth(*args, C.byref(depth_grads), self._stream())
-            _capi.check(st, "segs_rasterize_backward_depth")
-        else:
-            st = self._lib.segs_rasterize_backward(*args, self._stream())
-            _capi.check(st, "segs_rasterize_backward")
-        return g
+            depth_grads = _capi.DepthGrads(*(t.data_ptr() if t is not None else None for t in (dL_ddepth, dL_dalpha)))
+        self._call(*self._backward_args(dL_dout_color, depth_grads, camera_out))
+        return self.grads
 
 
 class KernelProfile:

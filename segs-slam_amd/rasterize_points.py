@@ -73,83 +73,52 @@ class _ResizableBuffer:
         return _capi.ALLOC_FN(_alloc)
 
 
-def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                           viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                           prefiltered):
-    """-> (num_rendered, out_color(3,H,W), radii(P) int32, geomBuffer, binningBuffer, imgBuffer)."""
+def _forward_args(tensors, gcb, bcb, icb, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, out_color, radii, maps, n):
+    """-> (entry point, its arguments without the stream, which goes before the last).  `tensors`: float32 and contiguous, in the
+    entry point's order; maps = (out_depth, out_alpha) selects the `_depth` twin, () the plain forward.  Needs no device."""
+    bg, m3, shc, col, opa, sca, rot, cov, view, proj, cam = tensors
+    M = int(shc.size(1)) if shc.numel() != 0 else 0
+    args = (gcb, None, bcb, None, icb, None, int(m3.size(0)), int(degree), M, _ptr(bg), int(out_color.size(2)), int(out_color.size(1)),
+            _ptr(m3), _ptr(shc), _ptr(col), _ptr(opa), _ptr(sca), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj),
+            _ptr(cam), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(out_color), _ptr(radii))
+    if maps:
+        dout = _capi.DepthOutputs(*(t.data_ptr() for t in maps))
+        return "segs_rasterize_forward_depth", args + (C.byref(dout), C.byref(n))
+    return "segs_rasterize_forward", args + (C.byref(n),)
+
+
+def _rasterize_forward(with_maps, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                       projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered):
+    """-> (num_rendered, out_color, radii, [out_depth, out_alpha,] geomBuffer, binningBuffer, imgBuffer)."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # AT_ERROR, rasterize_points.cu:57-59
     _require_gpu(means3D, "means3D")
     dev = means3D.device
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    # the reference zero-fills both (:68-69); that only shows for P == 0 (:81) -- otherwise every pixel and radius is written
+    # the reference zero-fills its outputs (:68-69); that only shows for P == 0 (:81) -- otherwise every pixel and radius is written
     mk = torch.empty if P != 0 else torch.zeros
     out_color = mk((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
+    maps = tuple(mk((H, W), dtype=torch.float32, device=dev) for _ in range(2)) if with_maps else ()
     radii = mk((P,), dtype=torch.int32, device=dev)
-    geom, binning, img = _ResizableBuffer(dev), _ResizableBuffer(dev), _ResizableBuffer(dev)
-    rendered = 0
-    if P != 0:  # rasterize_points.cu:81 (P == 0 leaves the zero image, not the background)
-        M = int(sh.size(1)) if sh.numel() != 0 else 0
+    buffers = [_ResizableBuffer(dev) for _ in range(3)]
+    n = C.c_int(0)
+    if P != 0:  # rasterize_points.cu:81 (P == 0 leaves the zero image and maps, not the background)
         keep = [_f32c(t) for t in (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp,
                                    viewmatrix, projmatrix, campos)]
-        bg, m3, shc, col, opa, sca, rot, cov, view, proj, cam = keep
-        n = C.c_int(0)
-        gcb, bcb, icb = geom.callback(), binning.callback(), img.callback()
+        name, args = _forward_args(keep, *(b.callback() for b in buffers), degree, scale_modifier, tan_fovx, tan_fovy, prefiltered,
+                                   out_color, radii, maps, n)
         with torch.cuda.device(dev):
-            st = _capi.lib().segs_rasterize_forward(
-                gcb, None, bcb, None, icb, None, P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(shc),
-                _ptr(col), _ptr(opa), _ptr(sca), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj),
-                _ptr(cam), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(out_color), _ptr(radii),
-                _stream(dev), C.byref(n))
-        _capi.check(st, "segs_rasterize_forward")
-        rendered = int(n.value)
-    return rendered, out_color, radii, geom.tensor, binning.tensor, img.tensor
+            st = getattr(_capi.lib(), name)(*args[:-1], _stream(dev), args[-1])
+        _capi.check(st, name)
+    return (int(n.value), out_color, radii, *maps, *(b.tensor for b in buffers))
 
 
-def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                                   viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                   geomBuffer, R, binningBuffer, imageBuffer):
-    """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)."""
-    _require_gpu(means3D, "means3D")
-    dev = means3D.device
-    P, H, W = int(means3D.size(0)), int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
-    opts = dict(dtype=torch.float32, device=dev)
-    # The kernels write every row, so empty() replaces the reference's nine torch::zeros fills (:149-157).
-    dL_dmeans3D = torch.empty((P, 3), **opts)
-    dL_dmeans2D = torch.empty((P, 3), **opts)
-    dL_dcolors = torch.empty((P, NUM_CHANNELS), **opts)
-    # dL_dconic (P,2,2) is an internal product of the reference's backward (:153), never returned: not materialised here
-    dL_dopacity = torch.empty((P, 1), **opts)
-    dL_dcov3D = torch.empty((P, 6), **opts)
-    dL_dsh = torch.zeros((P, M, 3), **opts)
-    has_sr = scales.numel() != 0
-    dL_dscales = torch.empty((P, 3), **opts) if has_sr else torch.zeros((P, 3), **opts)
-    dL_drotations = torch.empty((P, 4), **opts) if has_sr else torch.zeros((P, 4), **opts)
-    if P != 0:  # rasterize_points.cu:159
-        keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, campos, dL_dout_color)]
-        bg, m3, shc, col, sca, rot, cov, view, proj, cam, dL = keep
-        rad = radii.contiguous()
-        with torch.cuda.device(dev):
-            st = _capi.lib().segs_rasterize_backward(
-                P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sca),
-                float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx),
-                float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL),
-                _ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dmeans3D),
-                _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
-                _ptr(dL_drotations) if has_sr else None, _stream(dev))
-        _capi.check(st, "segs_rasterize_backward")
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
-
-
-def _depth_grad_ptr(t, H, W, name):
-    if t is None or t.numel() == 0:
-        return None
-    if tuple(t.shape) != (H, W):
-        raise RuntimeError(f"{name} must be (H, W) = ({H}, {W}), got {tuple(t.shape)}")
-    _require_gpu(t, name)
-    return t
+def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                           viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                           prefiltered):
+    """-> (num_rendered, out_color(3,H,W), radii(P) int32, geomBuffer, binningBuffer, imgBuffer)."""
+    return _rasterize_forward(False, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered)
 
 
 def RasterizeGaussiansDepthCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -158,35 +127,81 @@ def RasterizeGaussiansDepthCUDA(background, means3D, colors, opacity, scales, ro
     """RasterizeGaussiansCUDA plus the depth map sum z alpha T and the alpha map 1 - T_final of the same contributors
     (include/segs_raster.h, segs_rasterize_forward_depth).
     -> (num_rendered, out_color(3,H,W), radii(P), out_depth(H,W), out_alpha(H,W), geomBuffer, binningBuffer, imgBuffer)."""
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    return _rasterize_forward(True, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered)
+
+
+def _backward_args(tensors, radii, buffers, R, degree, scale_modifier, tan_fovx, tan_fovy, grads, map_grads=None, camera=None):
+    """-> (entry point, its arguments without the stream, which comes last).  `tensors`: float32 and contiguous, in the entry
+    point's order; `grads`: the wrappers' eight outputs.  map_grads = (dL_dout_depth, dL_dout_alpha), tensors or None, selects the
+    `_depth` form; camera = (dL_dviewmatrix, dL_dprojmatrix, temp) on top of it the `_camera` form.  Needs no device."""
+    bg, m3, shc, col, sca, rot, cov, view, proj, cam, dL = tensors
+    dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations = grads
+    M = int(shc.size(1)) if shc.numel() != 0 else 0
+    has_sr = sca.numel() != 0
+    # dL_dconic (P,2,2) is an internal product of the reference's backward (:153), never returned: not materialised (the None)
+    args = (int(m3.size(0)), int(degree), M, int(R), _ptr(bg), int(dL.size(2)), int(dL.size(1)), _ptr(m3), _ptr(shc), _ptr(col),
+            _ptr(sca), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx),
+            float(tan_fovy), _ptr(radii), *(_ptr(b) for b in buffers), _ptr(dL), _ptr(dL_dmeans2D), None, _ptr(dL_dopacity),
+            _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
+            _ptr(dL_drotations) if has_sr else None)
+    if map_grads is None:
+        return "segs_rasterize_backward", args
+    dg = _capi.DepthGrads(*(t.data_ptr() if t is not None else None for t in map_grads))   # passed even when both are NULL
+    if camera is None:
+        return "segs_rasterize_backward_depth", args + (C.byref(dg),)
+    cg = _capi.CameraGrads(*(t.data_ptr() for t in camera))
+    return "segs_rasterize_backward_camera", args + (C.byref(dg), C.byref(cg))
+
+
+def _map_grad(t, H, W, name):
+    if t is None or t.numel() == 0:
+        return None
+    if tuple(t.shape) != (H, W):
+        raise RuntimeError(f"{name} must be (H, W) = ({H}, {W}), got {tuple(t.shape)}")
+    _require_gpu(t, name)
+    return _f32c(t)
+
+
+def _rasterize_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                        tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
+                        map_grads=None, camera=False):
+    """map_grads = (dL_dout_depth, dL_dout_alpha): the depth form; camera=True on top: the camera form, two (4, 4) gradients more."""
     _require_gpu(means3D, "means3D")
     dev = means3D.device
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    mk = torch.empty if P != 0 else torch.zeros
-    out_color = mk((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
-    out_depth = mk((H, W), dtype=torch.float32, device=dev)
-    out_alpha = mk((H, W), dtype=torch.float32, device=dev)
-    radii = mk((P,), dtype=torch.int32, device=dev)
-    geom, binning, img = _ResizableBuffer(dev), _ResizableBuffer(dev), _ResizableBuffer(dev)
-    rendered = 0
-    if P != 0:  # as RasterizeGaussiansCUDA: P == 0 leaves zero maps
-        M = int(sh.size(1)) if sh.numel() != 0 else 0
-        keep = [_f32c(t) for t in (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp,
-                                   viewmatrix, projmatrix, campos)]
-        bg, m3, shc, col, opa, sca, rot, cov, view, proj, cam = keep
-        n = C.c_int(0)
-        gcb, bcb, icb = geom.callback(), binning.callback(), img.callback()
-        dout = _capi.DepthOutputs(out_depth.data_ptr(), out_alpha.data_ptr())
+    P, H, W = int(means3D.size(0)), int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    opts = dict(dtype=torch.float32, device=dev)
+    # The kernels write every row, so empty() replaces the reference's nine torch::zeros fills (:149-157) -- but for dL_dsh, and
+    # for dL_dscales / dL_drotations when the covariances came precomputed, which no kernel writes.
+    mk_sr = torch.empty if scales.numel() != 0 else torch.zeros
+    grads = tuple(torch.empty((P, n), **opts) for n in (3, NUM_CHANNELS, 1, 3, 6)) + (
+        torch.zeros((P, M, 3), **opts), mk_sr((P, 3), **opts), mk_sr((P, 4), **opts))
+    if map_grads is not None:
+        map_grads = (_map_grad(map_grads[0], H, W, "dL_dout_depth"), _map_grad(map_grads[1], H, W, "dL_dout_alpha"))
+    if camera:     # the library writes all 32 floats, zeros when nothing is rendered
+        camera = (torch.empty((4, 4), **opts), torch.empty((4, 4), **opts),
+                  torch.empty(_capi.lib().segs_camera_grad_temp_bytes(P), dtype=torch.uint8, device=dev))
+        grads += camera[:2]
+    if P != 0 or camera:  # rasterize_points.cu:159; the camera form is called for P == 0 too: the library zero-fills the two matrices
+        keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
+                                   projmatrix, campos, dL_dout_color)]
+        rad = radii.contiguous()
+        name, args = _backward_args(keep, rad, (geomBuffer, binningBuffer, imageBuffer), R, degree, scale_modifier, tan_fovx, tan_fovy,
+                                    grads[:8], map_grads, camera or None)
         with torch.cuda.device(dev):
-            st = _capi.lib().segs_rasterize_forward_depth(
-                gcb, None, bcb, None, icb, None, P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(shc),
-                _ptr(col), _ptr(opa), _ptr(sca), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj),
-                _ptr(cam), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(out_color), _ptr(radii),
-                C.byref(dout), _stream(dev), C.byref(n))
-        _capi.check(st, "segs_rasterize_forward_depth")
-        rendered = int(n.value)
-    return rendered, out_color, radii, out_depth, out_alpha, geom.tensor, binning.tensor, img.tensor
+            st = getattr(_capi.lib(), name)(*args, _stream(dev))
+        _capi.check(st, name)
+    return grads
+
+
+def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                                   viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
+                                   geomBuffer, R, binningBuffer, imageBuffer):
+    """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)."""
+    return _rasterize_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                               imageBuffer)
 
 
 def RasterizeGaussiansDepthBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -194,39 +209,9 @@ def RasterizeGaussiansDepthBackwardCUDA(background, means3D, radii, colors, scal
                                         sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer):
     """RasterizeGaussiansBackwardCUDA plus the gradients of the depth and alpha maps (H, W); either may be None or a
     0-element tensor (zero).  Same return tuple."""
-    _require_gpu(means3D, "means3D")
-    dev = means3D.device
-    P, H, W = int(means3D.size(0)), int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
-    opts = dict(dtype=torch.float32, device=dev)
-    dL_dmeans3D = torch.empty((P, 3), **opts)
-    dL_dmeans2D = torch.empty((P, 3), **opts)
-    dL_dcolors = torch.empty((P, NUM_CHANNELS), **opts)
-    dL_dopacity = torch.empty((P, 1), **opts)
-    dL_dcov3D = torch.empty((P, 6), **opts)
-    dL_dsh = torch.zeros((P, M, 3), **opts)
-    has_sr = scales.numel() != 0
-    dL_dscales = torch.empty((P, 3), **opts) if has_sr else torch.zeros((P, 3), **opts)
-    dL_drotations = torch.empty((P, 4), **opts) if has_sr else torch.zeros((P, 4), **opts)
-    gD = _depth_grad_ptr(dL_dout_depth, H, W, "dL_dout_depth")
-    gA = _depth_grad_ptr(dL_dout_alpha, H, W, "dL_dout_alpha")
-    gD, gA = (_f32c(t) if t is not None else None for t in (gD, gA))
-    if P != 0:
-        keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, campos, dL_dout_color)]
-        bg, m3, shc, col, sca, rot, cov, view, proj, cam, dL = keep
-        rad = radii.contiguous()
-        dg = _capi.DepthGrads(gD.data_ptr() if gD is not None else None, gA.data_ptr() if gA is not None else None)
-        with torch.cuda.device(dev):
-            st = _capi.lib().segs_rasterize_backward_depth(
-                P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sca),
-                float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx),
-                float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL),
-                _ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dmeans3D),
-                _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
-                _ptr(dL_drotations) if has_sr else None, C.byref(dg), _stream(dev))
-        _capi.check(st, "segs_rasterize_backward_depth")
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    return _rasterize_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                               imageBuffer, map_grads=(dL_dout_depth, dL_dout_alpha))
 
 
 def RasterizeGaussiansCameraBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -236,43 +221,9 @@ def RasterizeGaussiansCameraBackwardCUDA(background, means3D, radii, colors, sca
     independent (4, 4) input in its transposed layout (include/segs_raster.h, segs_rasterize_backward_camera).  `sh` must be
     absent: the SH colours depend on campos, which these gradients do not cover.
     -> the depth backward's tuple + (dL_dviewmatrix (4,4), dL_dprojmatrix (4,4))."""
-    _require_gpu(means3D, "means3D")
-    dev = means3D.device
-    P, H, W = int(means3D.size(0)), int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
-    opts = dict(dtype=torch.float32, device=dev)
-    dL_dmeans3D = torch.empty((P, 3), **opts)
-    dL_dmeans2D = torch.empty((P, 3), **opts)
-    dL_dcolors = torch.empty((P, NUM_CHANNELS), **opts)
-    dL_dopacity = torch.empty((P, 1), **opts)
-    dL_dcov3D = torch.empty((P, 6), **opts)
-    dL_dsh = torch.zeros((P, M, 3), **opts)
-    has_sr = scales.numel() != 0
-    dL_dscales = torch.empty((P, 3), **opts) if has_sr else torch.zeros((P, 3), **opts)
-    dL_drotations = torch.empty((P, 4), **opts) if has_sr else torch.zeros((P, 4), **opts)
-    dL_dview = torch.empty((4, 4), **opts)     # the library writes all 32 floats, zeros when nothing is rendered
-    dL_dproj = torch.empty((4, 4), **opts)
-    gD = _depth_grad_ptr(dL_dout_depth, H, W, "dL_dout_depth")
-    gA = _depth_grad_ptr(dL_dout_alpha, H, W, "dL_dout_alpha")
-    gD, gA = (_f32c(t) if t is not None else None for t in (gD, gA))
-    keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
-                               projmatrix, campos, dL_dout_color)]
-    bg, m3, shc, col, sca, rot, cov, view, proj, cam, dL = keep
-    rad = radii.contiguous()
-    lib = _capi.lib()
-    temp = torch.empty(lib.segs_camera_grad_temp_bytes(P), dtype=torch.uint8, device=dev)
-    dg = _capi.DepthGrads(gD.data_ptr() if gD is not None else None, gA.data_ptr() if gA is not None else None)
-    cg = _capi.CameraGrads(dL_dview.data_ptr(), dL_dproj.data_ptr(), temp.data_ptr())
-    with torch.cuda.device(dev):     # called for P == 0 too: the library zero-fills the two matrices
-        st = lib.segs_rasterize_backward_camera(
-            P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sca),
-            float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx),
-            float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL),
-            _ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dmeans3D),
-            _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales) if has_sr else None,
-            _ptr(dL_drotations) if has_sr else None, C.byref(dg), C.byref(cg), _stream(dev))
-    _capi.check(st, "segs_rasterize_backward_camera")
-    return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview, dL_dproj)
+    return _rasterize_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                               imageBuffer, map_grads=(dL_dout_depth, dL_dout_alpha), camera=True)
 
 
 def markVisible(means3D, viewmatrix, projmatrix):
