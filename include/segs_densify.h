@@ -49,6 +49,32 @@ int segs_anchor_growing_level(int A, int A_init, int n_offsets, int feat_dim, co
                               float cur_size, int max_new, float* new_anchor, float* new_feat, int* n_new, char* temp,
                               void* stream);
 
+/* Anchors from an RGB-D frame where the map renders nothing (no reference counterpart).
+ * Lattice: the pixels (u, v) = (stride/2 + i*stride, stride/2 + j*stride) inside the W x H image (integer division).
+ * target = the map segs_depth_target writes (Z where the sensor depth is valid, else 0); depth / alpha = the rasterizer's
+ * D (sum z alpha T) and A (1 - T_final) maps of the same view, or BOTH NULL when nothing was rendered (every valid lattice
+ * pixel then counts as unobserved: the first frame of a map, or A == 0).  Exactly one of the two NULL is
+ * SEGS_ERR_INVALID_ARGUMENT.  A lattice pixel is
+ *   valid      iff Z > 0
+ *   unobserved iff valid && A < alpha_max
+ *   in front   iff valid && use_front && A >= alpha_max && (D / A - Z) > front_abs + front_rel * Z
+ * and a candidate iff unobserved or in front.  Candidates are back-projected with the exact inverse of the rasterizer's
+ * projection (ndc2Pix, centred principal point), in float32 and in this order:
+ *   xv = ((2u+1)/W - 1) * tanfovx * Z,  yv = ((2v+1)/H - 1) * tanfovy * Z,
+ *   world_d = ((xv*M[0][d] + yv*M[1][d]) + Z*M[2][d]) + M[3][d],    g_d = (int)rintf(world_d / voxel_size)
+ * with M = cam_to_world: 16 floats in HOST memory, the inverse of the view matrix in the view matrix's own (transposed)
+ * layout.  A candidate with a g_d outside [-2^20, 2^20) is dropped and counted, never clamped.  The distinct voxels that
+ * remain and hold none of the A existing anchors (voxel of an anchor: segs_anchor_growing_level's, at voxel_size) become
+ * the rows g * voxel_size of new_anchor (max_new,3), in lexicographic voxel order.  n_new (1 device int) = their number
+ * even above max_new (only max_new rows are written).  counts (6 device words) = {valid lattice pixels, unobserved,
+ * in front, out of range, distinct candidate voxels, new anchors}.  Integer atomics only, no wait for the device: the
+ * same inputs give the same bytes on every run.  alpha_max must lie in (0, 1], stride >= 1, voxel_size > 0. */
+typedef struct { int stride; float alpha_max; int use_front; float front_abs, front_rel; float voxel_size; } segs_depth_seed_params;
+size_t segs_depth_seed_temp_bytes(int A, int H, int W, int stride);
+int segs_depth_seed(int A, const float* anchor, int H, int W, const float* target, const float* depth, const float* alpha,
+                    float tanfovx, float tanfovy, const float* cam_to_world, const segs_depth_seed_params* p, int max_new,
+                    float* new_anchor, int* n_new, uint32_t* counts, char* temp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,12 @@ class DepthLossParamsC(C.Structure):
     _fields_ = [("lambda_depth", C.c_float), ("lambda_alpha", C.c_float), ("alpha_min", C.c_float), ("normalize", C.c_int)]
 
 
+class DepthSeedParamsC(C.Structure):
+    """segs_depth_seed_params (include/segs_densify.h)."""
+    _fields_ = [("stride", C.c_int), ("alpha_max", C.c_float), ("use_front", C.c_int), ("front_abs", C.c_float),
+                ("front_rel", C.c_float), ("voxel_size", C.c_float)]
+
+
 class AdamSegment(C.Structure):
     """segs_adam_segment (include/segs_train.h)."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_double)]
@@ -64,6 +70,8 @@ SYMBOLS = {
     "segs_training_statis_guarded": (_i, [_i, _i] + [_vp] * 10),
     "segs_anchor_growing_temp_bytes": (_sz, [_i, _i]),
     "segs_anchor_growing_level": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_f, _f, _f, _i] + [_vp] * 5),
+    "segs_depth_seed_temp_bytes": (_sz, [_i, _i, _i, _i]),
+    "segs_depth_seed": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "segs_neural_set_flags": (C.c_uint, [C.c_uint]),
     "segs_neural_param_layout": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "segs_neural_temp_bytes": (_sz, [_vp, _i]),

@@ -10,6 +10,9 @@
 //                             sorted anchor keys  == selected_grid_coords_unique[~remove_duplicates]
 //   scan (3 small kernels)  : exclusive scan of the flags -> row of every new anchor
 //   emit_new_anchors_kernel : 32 lanes per new anchor: coords * cur_size, per-feature max over the voxel's run of parents
+//   depth_seed_kernel       : segs_depth_seed: thread = lattice pixel of an RGB-D frame; candidate test against the
+//                             rendered opacity / depth, back-projection, voxel key (or the sentinel) into the pixel's own slot;
+//                             then the same sort / run heads / binary search / scan as a growing level, and emit_seed_anchors_kernel
 // Built with -ffp-contract=off: xyz and the quantisation follow the reference's separate multiply / add / divide.
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -115,12 +118,26 @@ __global__ void __launch_bounds__(256) anchor_keys_kernel(int A, const float* __
   vals[a] = (uint32_t)a;
 }
 
+// SEEDING: keys with bit 63 set are the empty slots of segs_depth_seed (they sort behind every voxel) and head no run; the
+// run heads that remain are counted into *distinct (one integer atomic per wave).
+constexpr uint64_t EMPTY_KEY = ~0ull;
+template <bool SEEDING>
 __global__ void __launch_bounds__(256) survive_flags_kernel(int n, const uint64_t* __restrict__ ckeys, int A,
-                                                            const uint64_t* __restrict__ akeys, uint32_t* __restrict__ flags) {
+                                                            const uint64_t* __restrict__ akeys, uint32_t* __restrict__ flags,
+                                                            uint32_t* __restrict__ distinct) {
   const int i = blockIdx.x * 256 + threadIdx.x;
+  uint32_t f = 0u;
+  uint64_t k = 0;
+  if (i < n) {
+    k = ckeys[i];
+    f = (i == 0 || ckeys[i - 1] != k) ? 1u : 0u;            // head of its run: one row of unique_dim
+    if (SEEDING && (k >> 63)) f = 0u;
+  }
+  if (SEEDING) {
+    const uint64_t m = __ballot(f != 0u);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(distinct, (uint32_t)__popcll(m));
+  }
   if (i >= n) return;
-  const uint64_t k = ckeys[i];
-  uint32_t f = (i == 0 || ckeys[i - 1] != k) ? 1u : 0u;     // head of its run: one row of unique_dim
   if (f) {
     int lo = 0, hi = A;                                      // any anchor in this voxel? (:1601-1620)
     while (lo < hi) {
@@ -199,6 +216,12 @@ __global__ void __launch_bounds__(256) compact_heads_kernel(int n, const uint32_
   if (i < n && flags[i]) head_pos[excl[i]] = (uint32_t)i;
 }
 
+// coordinate f (0..2) of a packed voxel key, times the voxel size: selected_grid_coords_unique * cur_size (:1621)
+__device__ __forceinline__ float key_coord(uint64_t k, int f, float cur_size) {
+  const int g = (int)((k >> (42 - 21 * f)) & 0x1FFFFFu) - KEY_BIAS;
+  return (float)g * cur_size;
+}
+
 __global__ void __launch_bounds__(256) emit_new_anchors_kernel(int n, const int* __restrict__ n_new_dev, int max_new,
                                                                const uint32_t* __restrict__ head_pos, const uint64_t* __restrict__ ckeys,
                                                                const uint32_t* __restrict__ parents, const float* __restrict__ anchor_feat,
@@ -209,13 +232,70 @@ __global__ void __launch_bounds__(256) emit_new_anchors_kernel(int n, const int*
   if (v >= n_new) return;
   const uint32_t i0 = head_pos[v];
   const uint64_t k = ckeys[i0];
-  if (f < 3) {
-    const int g = (int)((k >> (42 - 21 * f)) & 0x1FFFFFu) - KEY_BIAS;
-    new_anchor[(size_t)v * 3 + f] = (float)g * cur_size;   // selected_grid_coords_unique * cur_size (:1621)
-  }
+  if (f < 3) new_anchor[(size_t)v * 3 + f] = key_coord(k, f, cur_size);
   float mx = -INFINITY;                                     // scatter_max over the voxel's candidates (:1632-1637)
   for (uint32_t i = i0; i < (uint32_t)n && ckeys[i] == k; i++) mx = fmaxf(mx, anchor_feat[(size_t)parents[i] * 32 + f]);
   new_feat[(size_t)v * 32 + f] = mx;
+}
+
+// ---- segs_depth_seed: anchors from the sensor depth where the map renders nothing
+// thread = lattice pixel (u, v) = (stride/2 + i*stride, stride/2 + j*stride).  ONE memory round trip deep, like stats_kernel:
+// the three map reads are requested together and unconditionally, the tests only select what is stored.  Every pixel writes
+// its OWN slot -- the voxel key of a candidate, EMPTY_KEY otherwise -- so the key array is the same on every run and its
+// length (the lattice size) is known to the host without reading a count back.  The four counters take one integer atomic
+// per wave each (ballot + popcount).
+struct SeedCam { float m[16]; };   // cam_to_world, row r column c at m[4 r + c]
+__global__ void __launch_bounds__(256) depth_seed_kernel(int n_lattice, int lattice_w, int stride, int H, int W,
+                                                         const float* __restrict__ target, const float* __restrict__ depth,
+                                                         const float* __restrict__ alpha, float tanfovx, float tanfovy, SeedCam M,
+                                                         float alpha_max, int use_front, float front_abs, float front_rel,
+                                                         float voxel_size, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                         uint32_t* __restrict__ counts) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const bool in = t < n_lattice;
+  const int j = in ? t / lattice_w : 0, i = in ? t - j * lattice_w : 0;
+  const int u = stride / 2 + i * stride, v = stride / 2 + j * stride;
+  const size_t pix = (size_t)v * W + u;
+  const float Z = in ? target[pix] : 0.f;
+  const float A = (in && alpha) ? alpha[pix] : 0.f;        // no render: nothing is observed
+  const float D = (in && depth) ? depth[pix] : 0.f;
+  const bool valid = Z > 0.f;
+  const bool unobserved = valid && A < alpha_max;
+  const bool front = valid && use_front != 0 && depth != nullptr && A >= alpha_max && (D / A - Z) > front_abs + front_rel * Z;
+  bool cand = unobserved || front;
+  uint64_t key = EMPTY_KEY;
+  bool out_of_range = false;
+  if (cand) {
+    const float xv = ((float)(2 * u + 1) / (float)W - 1.f) * tanfovx * Z;   // inverse of ndc2Pix and of the projection's x / (z tanfovx)
+    const float yv = ((float)(2 * v + 1) / (float)H - 1.f) * tanfovy * Z;
+    int g[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      const float world = ((xv * M.m[d] + yv * M.m[4 + d]) + Z * M.m[8 + d]) + M.m[12 + d];
+      const float r = rintf(world / voxel_size);                             // anchor_keys_kernel's quantisation
+      if (!(r >= (float)-KEY_BIAS && r < (float)KEY_BIAS)) out_of_range = true;   // (a NaN lands here too)
+      g[d] = out_of_range ? 0 : (int)r;
+    }
+    if (out_of_range) cand = false;                                          // dropped, not clamped into the border voxels
+    else key = pack_key(g[0], g[1], g[2]);
+  }
+  if (in) { keys[t] = key; vals[t] = (uint32_t)t; }
+  const uint64_t mv = __ballot(valid), mu = __ballot(unobserved), mf = __ballot(front), mo = __ballot(out_of_range);
+  if ((threadIdx.x & 63) == 0) {
+    if (mv) atomicAdd(counts + 0, (uint32_t)__popcll(mv));
+    if (mu) atomicAdd(counts + 1, (uint32_t)__popcll(mu));
+    if (mf) atomicAdd(counts + 2, (uint32_t)__popcll(mf));
+    if (mo) atomicAdd(counts + 3, (uint32_t)__popcll(mo));
+  }
+}
+
+__global__ void __launch_bounds__(256) emit_seed_anchors_kernel(const int* __restrict__ n_new_dev, int max_new,
+                                                                const uint32_t* __restrict__ head_pos, const uint64_t* __restrict__ ckeys,
+                                                                float voxel_size, float* __restrict__ new_anchor) {
+  const int e = blockIdx.x * 256 + threadIdx.x;            // element of the (n_new, 3) output
+  const int v = e / 3, f = e - v * 3;
+  if (v >= min(*n_new_dev, max_new)) return;
+  new_anchor[e] = key_coord(ckeys[head_pos[v]], f, voxel_size);
 }
 
 struct GrowTemp {
@@ -243,6 +323,21 @@ size_t grow_carve(int A, int nc, char* base, GrowTemp* t) {
   }
   return off;
 }
+
+// The part a growing level and a depth seeding share: flags of the run heads of the sorted candidate keys T.ckeys[0..n) whose
+// voxel holds none of the A sorted anchor keys, their exclusive scan (total -> *n_new) and the position of every surviving head.
+template <bool SEEDING>
+void new_voxel_heads(int n, int A, const GrowTemp& T, int* n_new, uint32_t* distinct, hipStream_t st) {
+  survive_flags_kernel<SEEDING><<<(n + 255) / 256, 256, 0, st>>>(n, T.ckeys, A, T.akeys, T.flags, distinct);
+  const int nblk = (n + SCAN_TILE - 1) / SCAN_TILE;
+  scan_block_sums<<<nblk, 256, 0, st>>>(n, T.flags, T.sums);
+  scan_sums_kernel<<<1, 1024, 0, st>>>(nblk, T.sums, n_new);
+  scan_apply<<<nblk, 256, 0, st>>>(n, T.flags, T.sums, T.excl);
+  compact_heads_kernel<<<(n + 255) / 256, 256, 0, st>>>(n, T.flags, T.excl, T.head_pos);
+}
+
+// lattice of segs_depth_seed: pixels stride/2 + i*stride below the image size
+int lattice_count(int size, int stride) { return size > stride / 2 ? (size - stride / 2 + stride - 1) / stride : 0; }
 
 }  // namespace
 
@@ -306,16 +401,57 @@ int segs_anchor_growing_level(int A, int A_init, int n_offsets, int feat_dim, co
   if (rc) return rc;
   rc = segs_sort_pairs(T.akeys_in, T.avals_in, T.akeys, T.avals, A, 63, T.sort_temp, stream);
   if (rc) return rc;
-  survive_flags_kernel<<<(n + 255) / 256, 256, 0, st>>>(n, T.ckeys, A, T.akeys, T.flags);
-  const int nblk = (n + SCAN_TILE - 1) / SCAN_TILE;
-  scan_block_sums<<<nblk, 256, 0, st>>>(n, T.flags, T.sums);
-  scan_sums_kernel<<<1, 1024, 0, st>>>(nblk, T.sums, n_new);
-  scan_apply<<<nblk, 256, 0, st>>>(n, T.flags, T.sums, T.excl);
-  compact_heads_kernel<<<(n + 255) / 256, 256, 0, st>>>(n, T.flags, T.excl, T.head_pos);
+  new_voxel_heads<false>(n, A, T, n_new, nullptr, st);
   const int cap = n < max_new ? n : max_new;
   if (cap > 0)
     emit_new_anchors_kernel<<<(cap + 7) / 8, 256, 0, st>>>(n, n_new, max_new, T.head_pos, T.ckeys, T.cvals, anchor_feat, cur_size,
                                                            new_anchor, new_feat);
+  e = hipGetLastError();
+  return e == hipSuccess ? SEGS_OK : segs::set_hip_error(e, __func__);
+}
+
+size_t segs_depth_seed_temp_bytes(int A, int H, int W, int stride) {
+  if (A < 0 || H <= 0 || W <= 0 || stride < 1 || (int64_t)H * W > INT32_MAX) return 0;
+  return grow_carve(A, lattice_count(H, stride) * lattice_count(W, stride), nullptr, nullptr);
+}
+
+int segs_depth_seed(int A, const float* anchor, int H, int W, const float* target, const float* depth, const float* alpha,
+                    float tanfovx, float tanfovy, const float* cam_to_world, const segs_depth_seed_params* p, int max_new,
+                    float* new_anchor, int* n_new, uint32_t* counts, char* temp, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (A < 0 || H <= 0 || W <= 0 || max_new < 0 || !p || p->stride < 1 || !(p->voxel_size > 0.f) || !(p->alpha_max > 0.f) ||
+      !(p->alpha_max <= 1.f) || (int64_t)H * W > INT32_MAX)
+    return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, "invalid argument (null pointer or bad size)");
+  if ((depth == nullptr) != (alpha == nullptr))
+    return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, "invalid argument (depth and alpha come together, or both NULL)");
+  if ((A > 0 && !anchor) || !target || !cam_to_world || (max_new > 0 && !new_anchor) || !n_new || !counts || !temp)
+    return segs::set_error(SEGS_ERR_INVALID_ARGUMENT, "invalid argument (null pointer or bad size)");
+  const int lw = lattice_count(W, p->stride), n = lattice_count(H, p->stride) * lw;
+  GrowTemp T;
+  grow_carve(A, n, temp, &T);
+  hipError_t e = hipMemsetAsync(counts, 0, 6 * sizeof(uint32_t), st);
+  if (e != hipSuccess) return segs::set_hip_error(e, __func__);
+  e = hipMemsetAsync(n_new, 0, sizeof(int), st);
+  if (e != hipSuccess) return segs::set_hip_error(e, __func__);
+  if (n == 0) return SEGS_OK;
+  SeedCam M;
+  for (int q = 0; q < 16; q++) M.m[q] = cam_to_world[q];   // a HOST pointer: the caller inverts the view matrix once per frame
+  depth_seed_kernel<<<(n + 255) / 256, 256, 0, st>>>(n, lw, p->stride, H, W, target, depth, alpha, tanfovx, tanfovy, M, p->alpha_max,
+                                                     p->use_front, p->front_abs, p->front_rel, p->voxel_size, T.ckeys_in, T.cvals_in,
+                                                     counts);
+  int rc = segs_sort_pairs(T.ckeys_in, T.cvals_in, T.ckeys, T.cvals, n, 64, T.sort_temp, stream);   // bit 63: the empty slots go last
+  if (rc) return rc;
+  if (A > 0) {
+    anchor_keys_kernel<<<(A + 255) / 256, 256, 0, st>>>(A, anchor, p->voxel_size, T.akeys_in, T.avals_in);
+    rc = segs_sort_pairs(T.akeys_in, T.avals_in, T.akeys, T.avals, A, 63, T.sort_temp, stream);
+    if (rc) return rc;
+  }
+  new_voxel_heads<true>(n, A, T, n_new, counts + 4, st);
+  e = hipMemcpyAsync(counts + 5, n_new, sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return segs::set_hip_error(e, __func__);
+  const int cap = n < max_new ? n : max_new;
+  if (cap > 0)
+    emit_seed_anchors_kernel<<<(cap * 3 + 255) / 256, 256, 0, st>>>(n_new, max_new, T.head_pos, T.ckeys, p->voxel_size, new_anchor);
   e = hipGetLastError();
   return e == hipSuccess ? SEGS_OK : segs::set_hip_error(e, __func__);
 }

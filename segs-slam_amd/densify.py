@@ -35,6 +35,43 @@ class DensifyParams:
     densify_grad_threshold: float = 0.0002
 
 
+@dataclass(frozen=True)
+class DepthSeedParams:
+    """Seeding anchors from an RGB-D frame where the map renders nothing (include/segs_densify.h: segs_depth_seed).
+
+    The defaults are conventions from the literature on RGB-D Gaussian mapping with silhouette-guided densification (an
+    opacity threshold of one half; "in front" = the sensor sees a surface nearer than the rendered one by a margin), not
+    values measured on this project's data.  `voxel_size` None = the densifier's own; `max_new` None = no cap below the
+    number of lattice pixels."""
+    stride: int = 4                  # every stride-th pixel in both directions, starting at stride // 2
+    alpha_max: float = 0.5           # a pixel the map covers less than this is unobserved
+    use_front: bool = False          # also seed where the sensor depth lies in front of the rendered depth D / A
+    front_abs: float = 0.05          # ... by more than front_abs + front_rel * Z (metres)
+    front_rel: float = 0.0
+    voxel_size: Optional[float] = None
+    max_new: Optional[int] = None
+
+    def __post_init__(self):
+        if int(self.stride) != self.stride or self.stride < 1:
+            raise ValueError("stride must be an integer >= 1")
+        if not 0.0 < self.alpha_max <= 1.0:
+            raise ValueError("alpha_max must lie in (0, 1]")
+        if self.voxel_size is not None and not self.voxel_size > 0.0:
+            raise ValueError("voxel_size must be positive")
+        if self.max_new is not None and self.max_new < 0:
+            raise ValueError("max_new must not be negative")
+
+
+SEED_COUNT_NAMES = ("valid lattice pixels", "unobserved", "in front", "out of range", "distinct voxels", "new anchors")
+
+
+def cam_to_world_of(view: torch.Tensor):
+    """inv(view) in float64, cast to float32, as a ctypes array of 16 floats in the view matrix's own (transposed) layout."""
+    import numpy as np
+    inv = np.linalg.inv(view.detach().cpu().numpy().astype(np.float64).reshape(4, 4)).astype(np.float32)
+    return (C.c_float * 16)(*inv.reshape(-1).tolist())
+
+
 class AnchorDensifier:
     def __init__(self, model: ScaffoldModel, params: Optional[DensifyParams] = None):
         self.model, self.p = model, params or DensifyParams()
@@ -136,6 +173,53 @@ class AnchorDensifier:
         if getattr(m, "coarse", None) is not None:        # :517-518: increasePcd -> increasePcdCoarse on the same points
             m.coarse.increase_pcd(points)
         return n_new
+
+    def seed_from_depth(self, kf, target: torch.Tensor, depth: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None,
+                        params: Optional[DepthSeedParams] = None) -> dict:
+        """New anchors at the voxels the sensor depth `target` ((H, W) map of a depth_loss.DepthTarget: Z where valid, else 0)
+        reaches and the map does not cover: lattice pixels whose rendered opacity `alpha` is below alpha_max (or, with
+        use_front, whose rendered depth lies behind the sensor's), back-projected through keyframe `kf`, one anchor per voxel
+        that holds none yet (segs_depth_seed).  `depth` / `alpha`: the rasterizer's maps of `kf`; both None = nothing was
+        rendered, every valid pixel seeds.  The new rows get zero offsets and features, log(voxel_size) scales, identity
+        rotation, opacity 0.1, zero Adam moments and zero statistics.  Returns the six counts of the call (one host read)."""
+        m = self.model
+        p = params or DepthSeedParams()
+        if getattr(m, "coarse", None) is not None:
+            raise ValueError("seed_from_depth: a model with a coarse anchor set has no rule for the coarse payload of seeded rows")
+        if (depth is None) != (alpha is None):
+            raise ValueError("depth and alpha come together (the rasterizer's two maps), or both None")
+        H, W = int(target.shape[-2]), int(target.shape[-1])
+        for t, what in ((target, "target"), (depth, "depth"), (alpha, "alpha")):
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise RuntimeError(f"{what} is not on the GPU: there is no CPU path")
+            if tuple(t.shape) != (H, W) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous float32 ({H}, {W}) map, not {t.dtype} {tuple(t.shape)}")
+        voxel = float(torch.tensor(self.p.voxel_size if p.voxel_size is None else p.voxel_size, dtype=torch.float32))
+        cp = _capi.DepthSeedParamsC(int(p.stride), float(p.alpha_max), int(bool(p.use_front)), float(p.front_abs),
+                                    float(p.front_rel), voxel)
+        n_lattice = len(range(p.stride // 2, H, p.stride)) * len(range(p.stride // 2, W, p.stride))
+        max_new = n_lattice if p.max_new is None else min(int(p.max_new), n_lattice)
+        dev = m.device
+        temp = torch.empty(self._lib.segs_depth_seed_temp_bytes(m.A, H, W, int(p.stride)), dtype=torch.uint8, device=dev)
+        new_anchor = torch.empty((max(max_new, 1), 3), dtype=torch.float32, device=dev)
+        words = torch.zeros(8, dtype=torch.int32, device=dev)          # [0..6) counts, [6] n_new
+        st = self._lib.segs_depth_seed(m.A, _p(m.param("anchor")) if m.A > 0 else None, H, W, _p(target),
+                                       None if depth is None else _p(depth), None if alpha is None else _p(alpha),
+                                       float(kf.tanfovx), float(kf.tanfovy), cam_to_world_of(kf.view), C.byref(cp), max_new,
+                                       _p(new_anchor), C.c_void_p(words.data_ptr() + 24), _p(words), _p(temp), self._stream())
+        _capi.check(st, "segs_depth_seed")
+        host = words.tolist()
+        counts = dict(zip(SEED_COUNT_NAMES, host[:6]))
+        n_new = min(host[6], max_new)
+        counts["new anchors"] = n_new                                  # (what was appended: max_new may cap the device's count)
+        if n_new > 0:
+            A0, no = m.A, m.dims.n_offsets
+            self._append(new_anchor[:n_new], torch.zeros((n_new, m.dims.feat_dim), dtype=torch.float32, device=dev), voxel)
+            self._stats["offset_denom"][A0 * no:m.A * no] = 0
+            self._stats["offset_gradient_accum"][A0 * no:m.A * no] = 0
+        return counts
 
     def anchor_growing(self, grads: torch.Tensor, threshold: float, offset_mask: torch.Tensor, rands: List[torch.Tensor]):
         """:1559-1699.  grads (A_init*no,), offset_mask (A_init*no,) bool, rands[i] (A_init*no,) in [0,1)."""

@@ -152,12 +152,14 @@ def load_committed_config(rel_path: str) -> MapperConfig:
 
 
 def make_mapper_step(cfg: MapperConfig, model, width: int, height: int, spatial_lr_scale: float = 1.0, process_group=None,
-                     densify_seed: int = 0, depth_loss_lambda: Optional[float] = None):
+                     densify_seed: int = 0, depth_loss_lambda: Optional[float] = None, depth_seed=None):
     """The anchor-level step configured like GaussianMapper::trainForOneIteration (src/gaussian_mapper.cpp:823-1032) for
     this configuration: mapper loss (0.01 * scaling regulariser :926-928, row mask :917-922, FFT regularisers :930-945),
     densification schedule :961-968, background :61-67.  `depth_loss_lambda` (no reference counterpart): depth supervision
     with that weight on the pixels whose sensor depth lies strictly inside the configuration's (RGBD.min_depth, RGBD.max_depth),
-    the reference's own validity test (src/gaussian_mapper.cpp:1673-1676); None = the step as the reference runs it."""
+    the reference's own validity test (src/gaussian_mapper.cpp:1673-1676); None = the step as the reference runs it.
+    `depth_seed` (densify.DepthSeedParams, no reference counterpart): the step can seed anchors from a keyframe's sensor depth
+    where the map renders nothing (ScaffoldTrainerStep.seed_keyframe)."""
     from .densify import AnchorDensifier
     from .neural_gaussians import ScaffoldTrainerStep
     if cfg.use_coarse_anchor and getattr(model, "coarse", None) is None:
@@ -169,7 +171,7 @@ def make_mapper_step(cfg: MapperConfig, model, width: int, height: int, spatial_
         num = lambda k: float(cfg.raw.get(k, 0))     # noqa: E731  (an absent key reads as 0, like cv::FileNode)
         depth_loss = DepthLossParams(float(depth_loss_lambda), min_depth=num("RGBD.min_depth"), max_depth=num("RGBD.max_depth"))
     step = ScaffoldTrainerStep(model, width, height, cfg.opt, spatial_lr_scale, process_group, scaling_reg_weight=0.01,
-                               depth_loss=depth_loss)
+                               depth_loss=depth_loss, depth_seed=depth_seed)
     step.row_mask = True
     step.set_background(cfg.white_background)
     if cfg.use_frequency_regularization:

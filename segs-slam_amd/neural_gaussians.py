@@ -351,7 +351,7 @@ class ScaffoldTrainerStep:
 
     def __init__(self, model: ScaffoldModel, width: int, height: int, opt: Optional[ScaffoldOptimizationParams] = None,
                  spatial_lr_scale: float = 1.0, process_group=None, scaling_reg_weight: float = 0.0, pose_grad: bool = False,
-                 depth_loss=None):
+                 depth_loss=None, depth_seed=None):
         # scaling_reg_weight = 0.01 gives the mapper's loss (src/gaussian_mapper.cpp:926-928), 0 the trainer's (:89-90 of
         # src/gaussian_trainer.cpp); the mapper's FFT regularisers (:930-945): enable_frequency_regularization()
         self.scaling_reg_weight = float(scaling_reg_weight)
@@ -371,6 +371,8 @@ class ScaffoldTrainerStep:
         # One FusedDepthLoss per pyramid level, like the engines; `depth_terms` = {total, L_depth, L_alpha, used pixels} of the
         # last iteration (a view of device words; None after a colour-only one).
         self.depth_loss = depth_loss
+        # depth_seed (densify.DepthSeedParams): the engines also render depth and opacity, for seed_keyframe
+        self.depth_seed = depth_seed
         self._depth_fns = {}
         self.depth_terms = None
         self.engine = self._make_engine(self.neural.P_capacity, width, height)
@@ -425,7 +427,8 @@ class ScaffoldTrainerStep:
 
     def _make_engine(self, P: int, width: int, height: int) -> RasterEngine:
         return RasterEngine(P, width, height, self.model.device, resident=True, skip_nonpositive_opacity=True,
-                            camera_grad=self.pose_grad, render_depth=self.depth_loss is not None)
+                            camera_grad=self.pose_grad,
+                            render_depth=self.depth_loss is not None or self.depth_seed is not None)
 
     def _depth_fn(self):
         """The depth loss of the level in flight (None on a step without depth supervision)."""
@@ -667,6 +670,57 @@ class ScaffoldTrainerStep:
             loss = self._forward_backward(kf, gt, depth=gt_depth)
         self.model.grads.zero_()
         return loss
+
+    def _seed_target(self, gt_depth) -> torch.Tensor:
+        """The (H, W) map of valid sensor depths seed_keyframe reads: a prepared DepthTarget's own, or segs_depth_target of a raw
+        tensor with the step's depth bounds (depth_loss's min_depth / max_depth; a step without depth_loss has none: every
+        finite positive depth is valid)."""
+        from .depth_loss import DepthTarget, depth_shape
+        if isinstance(gt_depth, DepthTarget):
+            return gt_depth.map
+        fn = self._depth_fn()
+        if fn is not None:
+            return fn.target_of(gt_depth).map
+        H, W = depth_shape(gt_depth)
+        z = gt_depth.view(H, W) if gt_depth.is_contiguous() else gt_depth.reshape(H, W).contiguous()
+        if not z.is_cuda or z.dtype != torch.float32:
+            raise ValueError("a sensor depth is a float32 tensor on the GPU")
+        block = torch.empty(int(self._lib.segs_depth_target_floats(H, W)), dtype=torch.float32, device=self.model.device)
+        _capi.check(self._lib.segs_depth_target(_p(z), H, W, 0.0, 0.0, _p(block), self._stream()), "segs_depth_target")
+        return block[:H * W].view(H, W)
+
+    def seed_keyframe(self, kf: Keyframe, gt_depth) -> dict:
+        """New anchors where keyframe `kf`'s sensor depth `gt_depth` (tensor or depth_loss.DepthTarget) shows a surface and the
+        map renders nothing (step made with depth_seed; densify.AnchorDensifier.seed_from_depth).  Called once
+        per keyframe, between iterations: a forward only (none at all for an empty map), no loss, no gradient, no optimizer
+        step.  Returns the six counts.  Synchronises, like adjust_anchor; afterwards the step is where adjust_anchor leaves it
+        when anchors were added.  Keyframe-parallel: every rank calls it with the same frame (the call is deterministic, the
+        replicas stay identical)."""
+        if self.depth_seed is None:
+            raise ValueError("seed_keyframe needs a step made with depth_seed=DepthSeedParams(...)")
+        if self.densifier is None:
+            raise ValueError("seed_keyframe appends through the step's densifier: call enable_densification first")
+        from .depth_loss import depth_shape
+        H, W = depth_shape(gt_depth)
+        self._redo_if_dropped()              # (an iteration still in flight resolves its overflow word first)
+        self.use_level(W, H)
+        target = self._seed_target(gt_depth)
+        depth = alpha = None
+        if self.model.A > 0:
+            self.render(kf)
+            if self.engine.resident and not self.engine.check(raise_on_overflow=False):
+                self.render(kf)              # the resident scratch overflowed (first use of a size): this forward re-calibrates
+            depth, alpha = self.engine.out_depth, self.engine.out_alpha
+        ex = self._exchange()
+        if ex.sharded:                       # moments are only current inside each rank's shard: whole before the bucket may move
+            ex.gather(self.model.exp_avg)
+            ex.gather(self.model.exp_avg_sq)
+        counts = self.densifier.seed_from_depth(kf, target, depth, alpha, self.depth_seed)
+        if counts["new anchors"] > 0:
+            # engine capacity, visible_radii, the candidate buffers and the exchange's frozen-anchor segment follow the model's
+            # size at the next forward (render, _exchange), as after adjust_anchor; the captured iterations are of the old size
+            self._graphs.clear()
+        return counts
 
     def _row_mask_of(self, gt: torch.Tensor):
         """(mask or None, masked target).  Evaluated once per target tensor (one host read); targets without an all-zero
