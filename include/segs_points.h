@@ -41,6 +41,44 @@ int segs_search_neighborhood_depth(int N, int width, float fx, float fy, float c
                                    const float* pixels /*N,2*/, const uint8_t* has3D, const float* point3D_orig /*N,3*/,
                                    const float* colors, float* point3D_result /*N,3*/, float* colors_result /*N,3*/, void* stream);
 
+/* ---- stereo frames as depth frames: semi-global matching (csrc/stereo_sgm.hip; specification in DESIGN.md 3i).
+ * What the reference asks of cv::cuda::StereoSGM (src/gaussian_mapper.cpp:93-95, 1591-1610), written from the published
+ * algorithm (Hirschmueller's SGM over a centre-symmetric 9x7 census cost); parity with OpenCV's bytes is not claimed.
+ * Integer arithmetic throughout, a fixed launch sequence and no float atomics: the same inputs give the same bytes. */
+typedef struct SegsStereoParams {
+  int num_disparities;   /* D: 64, 128 or 256 */
+  int min_disparity;     /* dmin >= 0, D + dmin <= 2047 */
+  int P1, P2;            /* 0 <= P1 <= P2 <= 224: a path cost fits 8 bits */
+  int uniqueness_ratio;  /* u in [0, 100); 0 = off */
+  int paths;             /* 4 or 8 */
+  int lr_max_diff;       /* >= -1; -1 = no left-right check */
+  int median;            /* 0 or 1: 3x3 median of the raw disparities */
+} SegsStereoParams;
+
+/* Scratch of one call: the two census maps, the summed path costs S (H x W x D uint16, d fastest), the raw disparity before and
+ * after the median, and the right view's disparity.  0 for sizes segs_stereo_sgm refuses. */
+size_t segs_stereo_sgm_temp_bytes(int W, int H, int D, int paths);
+
+/* left, right: (H, W) uint8, rectified.  disp16: (H, W) int16 = 16 x disparity (4 fractional bits, min_disparity included) where
+ * valid and 16 (min_disparity - 1) where not, so that the reference's own test `disp / 16 > min_disparity` drops the invalid
+ * pixels.  depth (may be NULL): (H, W) float32 = fb16 / (float)disp16 where valid and disp16 > 0, else 0 -- the "no measurement"
+ * of segs_depth_target; fb16 = 16 fx baseline.  1 <= W, H <= 4096.  Any parameter outside the ranges above returns
+ * SEGS_ERR_INVALID_ARGUMENT before any launch.  No host synchronisation and no allocation. */
+int segs_stereo_sgm(const SegsStereoParams* params, int W, int H, const uint8_t* left, const uint8_t* right, int16_t* disp16,
+                    float* depth, float fb16, char* temp, void* stream);
+
+/* cvtColor(RGB2GRAY) + convertTo(CV_8UC1, 255) of src/gaussian_mapper.cpp:1599-1603 on a (3, H, W) float32 image:
+ * g = (0.299f R + 0.587f G) + 0.114f B, out = (uint8) min(max(rintf(255 g), 0), 255); NaN gives 0. */
+int segs_rgb_to_gray_u8(int W, int H, const float* rgb, uint8_t* out, void* stream);
+
+/* segs_stereo_sgm, and afterwards copies of its stages (each pointer may be NULL): the census maps (H, W) uint32, S (H, W, D)
+ * uint16, the raw disparity after the winner stage and after the median (H, W) uint16 (equal when median = 0; 0xFFFF = invalid),
+ * and the right view's disparity (H, W) int16 (-1 = none). */
+int segs_debug_stereo_sgm_stages(const SegsStereoParams* params, int W, int H, const uint8_t* left, const uint8_t* right,
+                                 int16_t* disp16, float* depth, float fb16, char* temp, uint32_t* census_left,
+                                 uint32_t* census_right, uint16_t* S, uint16_t* raw_winner, uint16_t* raw_median,
+                                 int16_t* disp_right, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

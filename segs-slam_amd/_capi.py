@@ -56,6 +56,12 @@ class DepthSeedParamsC(C.Structure):
                 ("front_rel", C.c_float), ("voxel_size", C.c_float)]
 
 
+class StereoParamsC(C.Structure):
+    """SegsStereoParams (include/segs_points.h)."""
+    _fields_ = [("num_disparities", C.c_int), ("min_disparity", C.c_int), ("P1", C.c_int), ("P2", C.c_int),
+                ("uniqueness_ratio", C.c_int), ("paths", C.c_int), ("lr_max_diff", C.c_int), ("median", C.c_int)]
+
+
 class AdamSegment(C.Structure):
     """segs_adam_segment (include/segs_train.h)."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_double)]
@@ -126,6 +132,10 @@ SYMBOLS.update({
     "segs_scale_and_transform_points": (_i, [_i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "segs_reproject_depths_pinhole": (_i, [_i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "segs_search_neighborhood_depth": (_i, [_i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "segs_stereo_sgm_temp_bytes": (_sz, [_i, _i, _i, _i]),
+    "segs_stereo_sgm": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "segs_rgb_to_gray_u8": (_i, [_i, _i, _vp, _vp, _vp]),
+    "segs_debug_stereo_sgm_stages": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp] + [_vp] * 6 + [_vp]),
     "segs_l1_ssim_temp_bytes": (_sz, [_i, _i]),
     "segs_l1_ssim_tile_rows": (_i, [_i, _i]),
     "segs_l1_ssim_loss": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
