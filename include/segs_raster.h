@@ -72,6 +72,11 @@ const char* segs_last_error(void);
  * tolerance; slower on MI355X, where an f32 MFMA takes its cycles out of the SIMD's vector issue (DESIGN.md section 7.0,
  * tools/ubench_mfma_valu_overlap.hip).  Also switched on by the environment variable SEGS_RENDER_BWD_MFMA=1. */
 #define SEGS_RASTER_MFMA_MOMENTS 64u
+/* SEGS_RASTER_NO_WRITTEN_BYTES (A/B measurements and tests; resident backward entry points): withhold the "row written" bytes
+ * from the tile backward and the per-Gaussian backward, which then reads, converts and clears the accumulator row of every binned
+ * Gaussian instead of only the rows the tile backward added into.  Same gradients (an untouched row converts to zeros); slower
+ * wherever much of the scene is occluded.  Steps with and without the flag may alternate on the same buffers. */
+#define SEGS_RASTER_NO_WRITTEN_BYTES 128u
 uint32_t segs_raster_set_flags(uint32_t flags);
 
 /* Resident mode only, per host thread; returns the previous pointer.  When set, segs_rasterize_forward_resident also
@@ -162,6 +167,13 @@ int segs_debug_instance_values(const char* binning_buffer, int R, uint32_t* valu
 int segs_debug_unpack_image(const char* image_buffer, int width, int height, uint32_t* ranges /*tiles,2*/,
                             float* final_T /*H*W*/, uint32_t* n_contrib /*H*W*/, void* stream);
 
+/* Carve-up of the geometry scratch for P rows: (offset from the buffer's 256-byte-aligned base, bytes in use) of each region, in
+ * this order: records, bin records, offsets, internal radii, workgroup sums, clamp flags, status words, gradient accumulator
+ * rows, dense tile counts, "row written" bytes.  `regions` must be SEGS_GEOMETRY_REGIONS.  Host only; for tests, and for tools
+ * that look into a resident buffer (after any resident backward its accumulator rows and bytes are all zero again). */
+#define SEGS_GEOMETRY_REGIONS 10
+int segs_debug_geometry_layout(int P, size_t* offset_and_bytes /* 2 x regions */, int regions);
+
 /* Backward of the per-Gaussian stage alone (K12+K13) from caller-supplied dL_dmean2D (P,3) and dL_dconic
  * (P,2,2): lets a test check it bit-exactly against the oracle. */
 int segs_debug_preprocess_backward(int P, int width, int height, const float* means3D, const int* radii,
@@ -185,7 +197,8 @@ int segs_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* 
  * (Gaussian, tile) instances.  `status` is 4 device words: [0] = num_rendered R (instances binned), [1] = instances live after the dead ones were dropped, [3] = 1 if R exceeded the capacity
  * (outputs of that call are then meaningless; re-run with a larger capacity).  geom_buffer must be ZERO-FILLED before its
  * first use: the resident backward does not clear the per-Gaussian gradient accumulators inside it with a fill per call,
- * it writes zeros back over each row it consumes (a buffer that is clean stays clean).  The reference has no counterpart: its
+ * it writes zeros back over each row it consumes (a buffer that is clean stays clean), and over the "row written" byte the tile
+ * backward sets next to every row it adds into, which tells it which rows those are.  The reference has no counterpart: its
  * forward always blocks on a device-to-host copy of R (rasterizer_impl.cu:281). */
 size_t segs_resident_binning_bytes(int P, int capacity);
 int segs_rasterize_forward_resident(char* geom_buffer, char* binning_buffer, char* image_buffer, int capacity,

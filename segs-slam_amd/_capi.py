@@ -86,6 +86,7 @@ SYMBOLS = {
     "segs_neural_backward": (_i, [_vp, _i] + [_vp] * 17 + [_f, _vp, _vp, _vp]),
     "segs_neural_backward_camera": (_i, [_vp, _i] + [_vp] * 17 + [_f, _vp, _vp, _vp, _vp]),
     "segs_geometry_bytes": (_sz, [_i]),
+    "segs_debug_geometry_layout": (_i, [_i, _vp, _i]),
     "segs_image_bytes": (_sz, [_i, _i]),
     "segs_binning_bytes": (_sz, [_i]),
     "segs_rasterize_forward": (_i, [ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp,

@@ -192,6 +192,7 @@ struct Geom {
   uint32_t* clamped() const { return (uint32_t*)(base + L.clamped); }
   float* gacc() const { return (float*)(base + L.gacc); }
   uint32_t* touched() const { return (uint32_t*)(base + L.touched); }
+  uint8_t* written() const { return (uint8_t*)(base + L.written); }
 };
 Geom geom_at(char* p, int P) { return Geom{geom_layout(P), align_ptr(p)}; }
 // Resident buffers are carved up for the `rows` they were ALLOCATED (and zero-filled) for, so that the self-cleaned
@@ -369,6 +370,18 @@ uint32_t segs_raster_set_flags(uint32_t flags) {
 
 size_t segs_geometry_bytes(int P) { return geom_layout(P < 0 ? 0 : P).total; }
 size_t segs_image_bytes(int width, int height) { return image_layout(width, height).total; }
+
+int segs_debug_geometry_layout(int P, size_t* offset_and_bytes, int regions) {
+  if (P < 0 || !offset_and_bytes || regions != SEGS_GEOMETRY_REGIONS) return fail(SEGS_ERR_INVALID_ARGUMENT, "bad P / region count");
+  const GeomLayout g = geom_layout(P);
+  const size_t p = (size_t)P;
+  const size_t v[SEGS_GEOMETRY_REGIONS][2] = {
+      {g.rec, p * REC_DWORDS * 4}, {g.bin, p * sizeof(BinInfo)}, {g.offsets, p * 4}, {g.radii_internal, p * 4},
+      {g.block_sums, (size_t)(g.nblocks + 1) * 4 * 3}, {g.clamped, p * 4}, {g.num_rendered, 64}, {g.gacc, p * GACC_DWORDS * 4},
+      {g.touched, p * 4}, {g.written, p}};
+  for (int i = 0; i < SEGS_GEOMETRY_REGIONS; i++) { offset_and_bytes[2 * i] = v[i][0]; offset_and_bytes[2 * i + 1] = v[i][1]; }
+  return SEGS_OK;
+}
 size_t segs_binning_bytes(int num_rendered) { return binning_layout(num_rendered < 0 ? 0 : num_rendered).total; }
 
 static int rasterize_forward_impl(segs_alloc_fn geometry_alloc, void* geometry_ctx, segs_alloc_fn binning_alloc, void* binning_ctx,
@@ -490,7 +503,12 @@ int segs_rasterize_forward_depth(segs_alloc_fn geometry_alloc, void* geometry_ct
 
 // self_clean (resident entry point): the per-Gaussian accumulator rows are not cleared by a memset before the tile kernel;
 // preprocess_bwd_kernel writes zeros back over every row it consumes, so a buffer that starts out zero-filled is clean
-// again after every backward (one 32 MB fill and its launch less per iteration).
+// again after every backward (one 32 MB fill and its launch less per iteration).  The same holds for the "row written" bytes
+// (gs_layout.h) that only this form uses: the tile backward sets them, preprocess_bwd_kernel reads and clears only the rows
+// that carry one.  Invariant: after any resident backward -- of a valid step, of one the device drops (instance capacity
+// exceeded, depth key out of range: its tile kernels walk truncated lists, but still set a byte with every row they add into)
+// or of one that is redone -- every accumulator row and every byte is zero again.  The synchronising form clears the caller's
+// scratch with its memset per call and hands the kernels no bytes: it reads every binned row, as before.
 static int rasterize_backward_impl(int P, int D, int M, int R, const float* background, int width, int height,
                             const float* means3D, const float* shs, const float* scales,
                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
@@ -530,12 +548,13 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
   const float* dL_ddepth = dgrad ? dgrad->dL_ddepth : nullptr;
   const float* dL_dalpha = dgrad ? dgrad->dL_dalpha : nullptr;
   const bool depth_form = dL_ddepth || dL_dalpha;
+  uint8_t* const written = (self_clean && !(g_flags & SEGS_RASTER_NO_WRITTEN_BYTES)) ? G.written() : nullptr;
   if (R > 0 && depth_form) {
     { PROF(K_RENDER_BWD);
     render_bwd_depth_kernel<<<(gx * gy + 7) / 8 * 32, 64, 0, st>>>((const uint2*)(img + IL.ranges), (const uint32_t*)(bin + BL.vals[0]), width,
                                                                   height, G.rec(), background, (const float*)(img + IL.final_T),
                                                                   (const uint32_t*)(img + IL.n_contrib), dL_dpix, G.gacc(), gx * gy,
-                                                                  dL_ddepth, dL_dalpha);
+                                                                  dL_ddepth, dL_dalpha, written);
     }
     LAUNCH_TRY("render_bwd_depth_kernel");
   } else if (R > 0) {
@@ -543,7 +562,7 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
     static const bool mfma_env = [] { const char* e = getenv("SEGS_RENDER_BWD_MFMA"); return e && e[0] == '1'; }();   // measurement A/B only
     ((mfma_env || (g_flags & SEGS_RASTER_MFMA_MOMENTS)) ? render_bwd_mfma_kernel : render_bwd_kernel)<<<(gx * gy + 7) / 8 * 32, 64, 0, st>>>((const uint2*)(img + IL.ranges), (const uint32_t*)(bin + BL.vals[0]), width,
                                                     height, G.rec(), background, (const float*)(img + IL.final_T),
-                                                    (const uint32_t*)(img + IL.n_contrib), dL_dpix, G.gacc(), gx * gy);
+                                                    (const uint32_t*)(img + IL.n_contrib), dL_dpix, G.gacc(), gx * gy, written);
     }
     LAUNCH_TRY("render_bwd_kernel");
   }
@@ -556,7 +575,7 @@ static int rasterize_backward_impl(int P, int D, int M, int R, const float* back
                                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x, focal_y,
                                                      tan_fovx, tan_fovy, G.gacc(), (float)width, (float)height, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
                                                      dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, self_clean ? 1 : 0, nullptr,
-                                                     cam_live ? camera_partials(cam) : nullptr);
+                                                     cam_live ? camera_partials(cam) : nullptr, written);
   LAUNCH_TRY("preprocess_bwd_kernel");
   if (cam_live)
     if (int rc = camera_grads_finish(cam, G.L.nblocks, st)) return rc;
@@ -738,7 +757,7 @@ int segs_debug_preprocess_backward(int P, int width, int height, const float* me
                                                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x, focal_y,
                                                          tan_fovx, tan_fovy, nullptr, (float)width, (float)height, const_cast<float*>(dL_dmean2D),
                                                          const_cast<float*>(dL_dconic), nullptr, nullptr, dL_dmean3D, dL_dcov3D,
-                                                         dL_dscale, dL_drot, 0, nullptr, nullptr);
+                                                         dL_dscale, dL_drot, 0, nullptr, nullptr, nullptr);
   LAUNCH_TRY("preprocess_bwd_kernel");
   return SEGS_OK;
 }
@@ -764,7 +783,7 @@ int segs_debug_preprocess_backward_camera(int P, int width, int height, const fl
   (dL_dz ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<false, true>)<<<nblocks, 256, 0, st>>>(
       P, means3D, radii, cov3D_precomp ? nullptr : scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, focal_x,
       focal_y, tan_fovx, tan_fovy, nullptr, (float)width, (float)height, const_cast<float*>(dL_dmean2D), const_cast<float*>(dL_dconic),
-      nullptr, nullptr, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, 0, dL_dz, camera_partials(camera_grads));
+      nullptr, nullptr, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, 0, dL_dz, camera_partials(camera_grads), nullptr);
   LAUNCH_TRY("preprocess_bwd_kernel");
   return camera_grads_finish(camera_grads, nblocks, st);
 }

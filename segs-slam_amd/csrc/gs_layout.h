@@ -50,12 +50,15 @@ constexpr int MAX_GAUSSIANS = 1 << ID_BITS;
 // [5] dL/dopacity (= S0 / opacity)  [6,7,8] dL/dcolor  [9] dL/dz of the view depth (depth backward only; 0 otherwise).
 // Every row clear, by the memset of the synchronising backward or the write-back of preprocess_bwd_kernel, covers [0..11].
 constexpr int GACC_DWORDS = 16;
+// "Row written" byte, one per Gaussian (GeomLayout::written): the tile backward stores 1 next to every row it adds into, and the
+// per-Gaussian backward reads, converts and clears only those rows (resident backward; zero-filled with the arena, cleared by
+// its reader).  A byte, not a bit: concurrent writers all store the same 1, so nobody needs an atomic.
 
 constexpr size_t ALIGN = 256;
 inline size_t align_up(size_t v, size_t a = ALIGN) { return (v + a - 1) / a * a; }
 
 struct GeomLayout {
-  size_t rec, bin, offsets, radii_internal, block_sums, clamped, num_rendered, gacc, touched, total;
+  size_t rec, bin, offsets, radii_internal, block_sums, clamped, num_rendered, gacc, touched, written, total;
   int P, nblocks;
 };
 // Mirrors GeometryState::fromChunk (rasterizer_impl.cu:155-170) in role, not in layout.
@@ -73,6 +76,7 @@ inline GeomLayout geom_layout(int P) {
   g.num_rendered = o;   o = align_up(o + 64);
   g.gacc = o;           o = align_up(o + (size_t)P * GACC_DWORDS * 4);
   g.touched = o;        o = align_up(o + (size_t)P * 4);  // tiles_touched once more, dense: the depth-ordered prefix gathers 4 B, not a 16-B BinInfo
+  g.written = o;        o = align_up(o + (size_t)P);      // one "row written" byte per accumulator row
   g.total = o + ALIGN;  // slack so the base pointer can be aligned up
   return g;
 }

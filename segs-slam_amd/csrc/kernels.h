@@ -38,6 +38,8 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, co
 
 // DEPTH: + row dword [9] (dL/dz of the depth map, render_bwd_depth_kernel) into dL/dmean3D
 // CAM: + one row of 24 partial sums of dL/dviewmatrix and dL/dprojmatrix per workgroup into cam_partials (dz_in: see preprocess.hip)
+// written (with gacc; null = every binned row is read): the tile backward's "row written" bytes (gs_layout.h).  Only rows whose
+// byte is set are read, converted and -- with clean_gacc -- cleared together with their bytes; every other row writes zeros.
 constexpr int CAM_SUMS = 24;   // 12 live entries of each 4x4 gradient
 template <bool DEPTH, bool CAM>
 __global__ void preprocess_bwd_kernel(
@@ -48,7 +50,7 @@ __global__ void preprocess_bwd_kernel(
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int clean_gacc,
-    const float* __restrict__ dz_in, float* __restrict__ cam_partials);
+    const float* __restrict__ dz_in, float* __restrict__ cam_partials, uint8_t* __restrict__ written);
 __global__ void camera_grad_reduce_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ dL_dview,
                                           float* __restrict__ dL_dproj);
 __global__ void sh_backward_kernel(int P, const float* __restrict__ means3D, const int* __restrict__ radii,
@@ -93,18 +95,21 @@ __global__ void identify_tile_ranges_kernel(int L, const uint32_t* __restrict__ 
                                             uint32_t* __restrict__ status_mirror, const uint32_t* __restrict__ n_live);
 
 // ---- render.hip
+// written (tile backwards; may be null): one byte per Gaussian, set to 1 next to every accumulator row a batch adds into.
 __global__ void render_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
                                   const float* __restrict__ rec, const float* __restrict__ bg,
                                   float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color);
 __global__ void render_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
                                   const float* __restrict__ rec, const float* __restrict__ bg,
                                   const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-                                  const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles);
+                                  const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+                                  uint8_t* __restrict__ written);
 // A/B partner of render_bwd_kernel: the Gaussian role's sums as v_mfma_f32_16x16x4_f32 instead of VALU FMAs (SEGS_RENDER_BWD_MFMA=1)
 __global__ void render_bwd_mfma_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
                                        const float* __restrict__ rec, const float* __restrict__ bg,
                                        const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-                                       const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles);
+                                       const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+                                       uint8_t* __restrict__ written);
 // Depth forms (no reference counterpart): render_fwd_kernel + out_depth = sum z alpha T and out_alpha = 1 - final_T (either may be
 // null); render_bwd_kernel + the gradients of those maps (either may be null), dL/dz into row dword [9].
 __global__ void render_fwd_depth_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
@@ -115,7 +120,8 @@ __global__ void render_bwd_depth_kernel(const uint2* __restrict__ ranges, const 
                                         const float* __restrict__ rec, const float* __restrict__ bg,
                                         const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
                                         const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
-                                        const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha);
+                                        const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
+                                        uint8_t* __restrict__ written);
 
 // ---- debug / test support (binning.hip)
 __global__ void unpack_geometry_kernel(int P, const float* __restrict__ rec, const BinInfo* __restrict__ bin,

@@ -282,6 +282,12 @@ __device__ __forceinline__ void quat_rows(float4 q, float R[3][3]) {   // standa
 // passes of eight values through the input sweeps' staging buffer, no LDS of its own -- and plain-stores 24 floats into
 // cam_partials[blockIdx.x]; camera_grad_reduce_kernel adds the workgroups' rows in a fixed order.  No atomics: the same
 // per-Gaussian inputs give the same bits.  dz_in (CAM only, gacc null): per-Gaussian dL/dz of the stage-alone debug entry.
+// written (with gacc; null = every binned Gaussian's row is read, as the synchronising backward and the A/B switch
+// SEGS_RASTER_NO_WRITTEN_BYTES want): the tile backward's "row written" bytes.  In a scene with occlusion most binned Gaussians
+// are never reached by the tile backward (about four in five at 3 M Gaussians / 1080p): their rows hold zeros, which this kernel
+// used to read, write back and push through the whole projection backward to arrive at zeros.  With the bytes only written rows
+// are read, cleared (together with their bytes, so the arena stays clean from step to step) and converted; every other lane
+// writes the zeros a culled Gaussian writes.  The byte is fetched with the input sweeps: no dependent round trip of its own.
 template <bool DEPTH, bool CAM>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
     int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,
@@ -292,11 +298,13 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     int clean_gacc /* write zeros back over the consumed accumulator row (resident backward) */,
-    const float* __restrict__ dz_in, float* __restrict__ cam_partials /* CAM: CAM_SUMS floats per workgroup */) {
+    const float* __restrict__ dz_in, float* __restrict__ cam_partials /* CAM: CAM_SUMS floats per workgroup */,
+    uint8_t* __restrict__ written) {
   __shared__ float lds[3 * 768];
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const bool live = idx < P;
-  const bool binned = live && radii[idx] > 0;
+  const bool row_written = (gacc && written) ? (live && written[idx] != 0) : live;   // in flight together with the sweeps below
+  const bool binned = live && radii[idx] > 0 && row_written;   // from here on: binned AND reached by the tile backward
   float3 mean, scale, unused;
   load_rows3(means3D, scales, nullptr, P, lds, mean, scale, unused);
 
@@ -317,8 +325,12 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
       __shared__ __attribute__((aligned(16))) float gl[4][32 * GACC_DWORDS];
       const int lane = threadIdx.x & 63;
       float* const wl = gl[threadIdx.x >> 6];
-      const uint64_t rows = __ballot(binned);   // only binned Gaussians' rows can have been touched by the tile kernel
+      // only binned Gaussians' rows can have been touched by the tile kernel; with the bytes, exactly the rows that were
+      const uint64_t rows = __ballot(written ? row_written : binned);
       const size_t wave_first = (size_t)blockIdx.x * 256 + (threadIdx.x & ~63);
+      // the consumed bytes: the wave's whole 64-byte run as sixteen dwords (the region is padded past P, gs_layout.h)
+      if (written && clean_gacc && rows != 0ull && lane < 16 && wave_first + 4 * lane < (size_t)P)
+        reinterpret_cast<uint32_t*>(written + wave_first)[lane] = 0u;
 #pragma unroll
       for (int half = 0; half < 2; half++) {
         float4 q[2];
@@ -539,7 +551,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(
 
 #define SEGS_PREPROCESS_BWD_ARGS int, const float*, const int*, const float*, const float*, float, const float*, const float*, \
     const float*, float, float, float, float, float*, float, float, float*, float*, float*, float*, float*, float*, float*, float*, int, \
-    const float*, float*
+    const float*, float*, uint8_t*
 template __global__ void preprocess_bwd_kernel<false, false>(SEGS_PREPROCESS_BWD_ARGS);
 template __global__ void preprocess_bwd_kernel<true, false>(SEGS_PREPROCESS_BWD_ARGS);
 template __global__ void preprocess_bwd_kernel<false, true>(SEGS_PREPROCESS_BWD_ARGS);

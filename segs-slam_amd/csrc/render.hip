@@ -318,7 +318,7 @@ __device__ __forceinline__ void render_bwd_body(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
-    const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha) {
+    const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha, uint8_t* __restrict__ written) {
   static_assert(!(MFMA && DEPTH), "the depth form of the tile backward is the VALU form");
   // One wave (one 8x8 quadrant) per workgroup: the four quadrants of a tile share nothing but their inputs, and as one
   // 256-thread workgroup the three shorter ones held their LDS and wave slots until the longest list ended (the longest
@@ -526,6 +526,7 @@ __device__ __forceinline__ void render_bwd_body(
       }
       }
       wave_lds_fence();
+      uint32_t id_gs;
       {
         // every lane of column gs shifts slot gs from quadrant-local moments to Gaussian-relative ones
         const float4 m0 = *reinterpret_cast<const float4*>(&mom[gs][0]);  // S0 S1x S1y Sxx
@@ -540,6 +541,7 @@ __device__ __forceinline__ void render_bwd_body(
         // S0 = sum of w = o * sum of G dL/dalpha leaves as dL/dopacity = S0 / o (backward.cu:554): the per-Gaussian backward
         // then needs no opacity -- and with its conic recomputed there, no record gather at all
         const float inv_o = fast_rcp(reinterpret_cast<const float*>(&L.rec[gs][1])[1]);
+        id_gs = __float_as_uint(reinterpret_cast<const float*>(&L.rec[gs][2])[2]);   // for the "row written" byte below: no wait of its own
         wave_lds_fence();
         if (part == 0) {
           *reinterpret_cast<float4*>(&mom[gs][0]) = make_float4(Mx, My, Mxx, Mxy);
@@ -560,6 +562,12 @@ __device__ __forceinline__ void render_bwd_body(
 #endif
         }
       }
+      // "row written" bytes (gs_layout.h), one lane per slot: the per-Gaussian backward reads and clears only the rows that carry one
+      if (written && lane < nb) {   // (lane < nb <= 16: gs == lane)
+        uint32_t one;   // made here, in the batch: as a plain constant it is hoisted and holds a register through the whole loop
+        asm volatile("v_mov_b32 %0, 1" : "=v"(one));
+        written[id_gs] = (uint8_t)one;
+      }
       wave_lds_fence();
     } while (taken < n);
     if (tail) break;
@@ -569,23 +577,25 @@ __device__ __forceinline__ void render_bwd_body(
 __global__ void __launch_bounds__(64) render_bwd_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
-    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles) {
-  render_bwd_body<false, false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, nullptr, nullptr);
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+    uint8_t* __restrict__ written) {
+  render_bwd_body<false, false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, nullptr, nullptr, written);
 }
 // The Gaussian role's sums on the matrix pipe: the measured A/B partner (SEGS_RENDER_BWD_MFMA=1, capi.hip).
 __global__ void __launch_bounds__(64) render_bwd_mfma_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
-    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles) {
-  render_bwd_body<true, false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, nullptr, nullptr);
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
+    uint8_t* __restrict__ written) {
+  render_bwd_body<true, false>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, nullptr, nullptr, written);
 }
 // The depth form (VALU Gaussian role): render_bwd_kernel plus the gradients of render_fwd_depth_kernel's depth and alpha maps.
 __global__ void __launch_bounds__(64) render_bwd_depth_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H,
     const float* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ gacc, uint32_t num_tiles,
-    const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha) {
-  render_bwd_body<false, true>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, dL_ddepth, dL_dalpha);
+    const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha, uint8_t* __restrict__ written) {
+  render_bwd_body<false, true>(ranges, point_list, W, H, rec, bg, final_T, n_contrib, dL_dpix, gacc, num_tiles, dL_ddepth, dL_dalpha, written);
 }
 
 }  // namespace segs

@@ -4,6 +4,7 @@ entries of a wave's quadrant per 64-entry chunk, batches of 16 when cut per chun
 work over workgroups (a tile's four waves end together only if their quadrants hold the same number of pairs).
 
 usage: python tools/tile_stats.py [workload ...]      (default: 1080p_3m c2_1080p)
+       python tools/tile_stats.py --touched [workload ...]   only the share of the binned Gaussians that the tile backward reaches
 """
 import ctypes as C
 import os
@@ -91,6 +92,28 @@ def stats(workload: str) -> None:
     print(f"   pixel evaluations {tot * 64} (pairs x 64); sum n_contrib {pix_useful}")
 
 
+def touched(workload: str) -> None:
+    """Binned Gaussians whose accumulator row the tile backward added into, counted by what the row turns into: a non-zero
+    dL/dcolor, dL/dopacity or dL/dmean2D (a row of zeros converts to zeros; dL/dimage of the seeded scenes is never zero)."""
+    dev = torch.device("cuda", 0)
+    sc = scenes.make_config_scene(workload, keyframe=0)
+    cam = sc.camera
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    eng = RasterEngine(sc.P, cam.width, cam.height, dev, resident=True)
+    args = (t(sc.bg), t(sc.means3D), t(sc.colors), t(sc.opacity), t(sc.scales), t(sc.rotations), t(cam.world_view_transform),
+            t(cam.full_proj_transform), t(cam.camera_center), cam.tanfovx, cam.tanfovy)
+    for _ in range(2):
+        eng.forward(*args)
+        g = eng.backward(t(sc.dL_dout_color))
+    eng.check()
+    binned = eng.radii > 0
+    hit = (g["colors"].abs().sum(1) + g["opacity"].abs().sum(1) + eng.dL_dmean2D.abs().sum(1)) != 0
+    nb, nh = int(binned.sum()), int((hit & binned).sum())
+    print(f"== {workload}: P {sc.P}, binned {nb}, reached by the tile backward {nh} = {nh / max(nb, 1):.3f} of the binned, "
+          f"{nh / sc.P:.3f} of all; reached but not binned {int((hit & ~binned).sum())}")
+
+
 if __name__ == "__main__":
-    for wl in (sys.argv[1:] or ["1080p_3m", "c2_1080p"]):
-        stats(wl)
+    names = [a for a in sys.argv[1:] if a != "--touched"]
+    for wl in (names or ["1080p_3m", "c2_1080p"]):
+        (touched if "--touched" in sys.argv[1:] else stats)(wl)
