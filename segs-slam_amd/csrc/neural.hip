@@ -2054,49 +2054,36 @@ static int neural_backward_impl(const segs_neural_dims* dims, int A, const float
   constexpr size_t pair_lds = pair_run > pair_end ? pair_run : pair_end;
   static_assert(bwd_lds <= 160 * 1024 && pair_lds + PAIR_CAM_LDS <= 160 * 1024, "one workgroup per CU");
   static_assert(pair_lds == pair_end, "the camera slots of the pair kernel follow the staging area");
-  auto allow_lds = [](const void* kernel, size_t bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-  const hipError_t attr_rc[4] = {allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<false>), bwd_lds),
-                                 allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<true>), bwd_lds),
-                                 allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<false>), pair_lds),
-                                 allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<true>), pair_lds)};
-  for (const hipError_t rc_attr : attr_rc)
-    if (rc_attr != hipSuccess) return segs::set_hip_error(rc_attr, __func__);
-  const bool cam = dL_dcamera_center != nullptr;
-  if (cam) {
-    const hipError_t cam_rc[4] = {allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<false, true>), bwd_lds),
-                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_kernel<true, true>), bwd_lds),
-                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<false, true>), pair_lds + PAIR_CAM_LDS),
-                                  allow_lds(reinterpret_cast<const void*>(neural_bwd_pair_kernel<true, true>), pair_lds + PAIR_CAM_LDS)};
-    for (const hipError_t rc_attr : cam_rc)
-      if (rc_attr != hipSuccess) return segs::set_hip_error(rc_attr, __func__);
-  }
   // the regulariser sum was cleared by the forward (pack_tables_kernel) and is cleared again by reg_finish_kernel; it is
   // only accumulated when somebody reads it
   float* reg_sum = scaling_reg_out ? T.gsum + L.total + 8 : nullptr;
   // Chain waves + weight-gradient waves (neural_bwd_pair_kernel; the feature-bank model too since round 4, its epilogue on
   // compact rows).  SEGS_NEURAL_ONE_KERNEL_BACKWARD (segs_neural_set_flags, segs_neural.h) selects the one-kernel form: the
   // A/B of profiles/ and tests/test_neural_gpu.py.
+  const bool cam = dL_dcamera_center != nullptr;
   const bool one_role = (g_neural_flags & SEGS_NEURAL_ONE_KERNEL_BACKWARD) != 0u;
-  if (cam && !one_role)
-    (L.bank ? neural_bwd_pair_kernel<true, true> : neural_bwd_pair_kernel<false, true>)<<<BWD_GRID, 512, pair_lds + PAIR_CAM_LDS, st>>>(
-        L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
-        dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
-        scaling_reg_weight, reg_sum);
-  else if (cam)
-    (L.bank ? neural_bwd_kernel<true, true> : neural_bwd_kernel<false, true>)<<<BWD_GRID, 256, bwd_lds, st>>>(
-        L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
-        dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
-        scaling_reg_weight, reg_sum);
-  else if (!one_role)
-    (L.bank ? neural_bwd_pair_kernel<true> : neural_bwd_pair_kernel<false>)<<<BWD_GRID, 512, pair_lds, st>>>(
-        L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
-        dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
-        scaling_reg_weight, reg_sum);
-  else
-    (L.bank ? neural_bwd_kernel<true> : neural_bwd_kernel<false>)<<<BWD_GRID, 256, bwd_lds, st>>>(
-        L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
-        dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
-        scaling_reg_weight, reg_sum);
+  // Every instantiation of the two forms, with the launch shape it runs with.  The plain call opts the plain ones into their
+  // dynamic LDS and the camera call all eight (a per-device attribute, set on every call as in the forward), in this order.
+  struct Form { decltype(&neural_bwd_kernel<false>) kernel; bool pair, bank, cam; int threads; size_t lds; };
+  const Form forms[8] = {{neural_bwd_kernel<false>, false, false, false, 256, bwd_lds},
+                         {neural_bwd_kernel<true>, false, true, false, 256, bwd_lds},
+                         {neural_bwd_pair_kernel<false>, true, false, false, 512, pair_lds},
+                         {neural_bwd_pair_kernel<true>, true, true, false, 512, pair_lds},
+                         {neural_bwd_kernel<false, true>, false, false, true, 256, bwd_lds},
+                         {neural_bwd_kernel<true, true>, false, true, true, 256, bwd_lds},
+                         {neural_bwd_pair_kernel<false, true>, true, false, true, 512, pair_lds + PAIR_CAM_LDS},
+                         {neural_bwd_pair_kernel<true, true>, true, true, true, 512, pair_lds + PAIR_CAM_LDS}};
+  const Form* form = nullptr;
+  for (const Form& f : forms) {
+    if (f.cam && !cam) continue;
+    const hipError_t rc_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
+    if (rc_attr != hipSuccess) return segs::set_hip_error(rc_attr, __func__);
+    if (f.pair == !one_role && f.bank == (L.bank != 0) && f.cam == cam) form = &f;
+  }
+  form->kernel<<<BWD_GRID, form->threads, form->lds, st>>>(
+      L, T.count, T.vis, anchor, offset, anchor_feat, scaling_log, T.images, (const Small*)T.small, camera_center, dL_dmeans3D,
+      dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_danchor, dL_doffset, dL_dfeat, dL_dscaling_log, T.rows, T.partial,
+      scaling_reg_weight, reg_sum);
   if (cam) camera_center_reduce_kernel<<<1, 64, 0, st>>>(T.count, T.cam_rows, dL_dcamera_center);
   if (scaling_reg_out && L.app == 0) reg_finish_kernel<<<1, 1, 0, st>>>(T.count, reg_sum, scaling_reg_weight, scaling_reg_out);
   const WJobs J = make_jobs(L, !one_role);
