@@ -15,7 +15,6 @@ The raster backend and the optimizer are injectable so that the distributed logi
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass, field
 from typing import Callable, Dict, Optional
@@ -23,8 +22,9 @@ from typing import Callable, Dict, Optional
 import torch
 import torch.distributed as dist
 
-from . import loss_utils
+from . import _capi, loss_utils
 from .raster_engine import FIELDS, FLOATS_PER_GAUSSIAN, split_flat
+from .step_shared import DroppedStepRedo, IterationStage, adam_step, ptr, stream_ptr
 
 
 @dataclass
@@ -107,9 +107,7 @@ class FusedAdam:
     guarded by a device word (the all-reduced overflow word of the resident rasterizer) and restricted to a shard."""
 
     def __init__(self, n_params: int, device, opt: OptimizationParams):
-        from . import _capi
-        self._capi = _capi
-        self._lib = _capi.lib()
+        _capi.lib()                      # (there is no CPU fallback: a missing library is an error here)
         self.opt = opt
         self.exp_avg = torch.zeros(n_params, dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(n_params, dtype=torch.float32, device=device)
@@ -123,25 +121,16 @@ class FusedAdam:
              exchange=None, guard: Optional[torch.Tensor] = None):
         groups = field_segments(lrs, P)
         if exchange is not None:
-            groups = exchange.clip_segments(groups) or [(0, 0, 0.0)]
-        segs = (self._capi.AdamSegment * len(groups))()
-        for i, (o, n, lr) in enumerate(groups):
-            segs[i].offset, segs[i].count, segs[i].lr = o, n, lr
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        call = self.count.eager_call()
-        st = self._lib.segs_adam_step_device(p(params_flat), p(grads_flat), p(self.exp_avg), p(self.exp_avg_sq), segs, len(groups),
-                                             self.opt.beta1, self.opt.beta2, self.opt.eps, p(self.count.words), call,
-                                             float(grad_scale), 1, p(guard) if guard is not None else None,
-                                             C.c_void_p(torch.cuda.current_stream(params_flat.device).cuda_stream))
-        self._capi.check(st, "segs_adam_step_device")
+            groups = exchange.clip_segments(groups)
+        adam_step((params_flat, grads_flat, self.exp_avg, self.exp_avg_sq), groups, self.opt, self.count, ptr(guard),
+                  params_flat.device, grad_scale)
 
 
 class FusedL1SSIM:
     """segs_l1_ssim_loss (include/segs_train.h): loss and dL/dimage in two HBM-streaming kernels."""
 
     def __init__(self, H: int, W: int, device, lambda_dssim: float):
-        from . import _capi
-        self._capi, self._lib = _capi, _capi.lib()
+        self._lib = _capi.lib()
         self.H, self.W, self.lam = int(H), int(W), float(lambda_dssim)
         self.temp = torch.empty(self._lib.segs_l1_ssim_temp_bytes(H, W), dtype=torch.uint8, device=device)
         self.out = torch.zeros(3, dtype=torch.float32, device=device)     # loss, l1, ssim
@@ -149,10 +138,9 @@ class FusedL1SSIM:
 
     def __call__(self, image: torch.Tensor, gt: torch.Tensor):
         assert image.is_contiguous() and gt.is_contiguous() and image.shape == (3, self.H, self.W) == gt.shape
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        st = self._lib.segs_l1_ssim_loss(p(image), p(gt), self.H, self.W, self.lam, p(self.out), p(self.dL), p(self.temp),
-                                         C.c_void_p(torch.cuda.current_stream(image.device).cuda_stream))
-        self._capi.check(st, "segs_l1_ssim_loss")
+        st = self._lib.segs_l1_ssim_loss(ptr(image), ptr(gt), self.H, self.W, self.lam, ptr(self.out), ptr(self.dL), ptr(self.temp),
+                                         stream_ptr(image.device))
+        _capi.check(st, "segs_l1_ssim_loss")
         return self.out[0], self.dL
 
 
@@ -187,7 +175,7 @@ class TorchAdam:
         grads_flat.zero_()
 
 
-class TrainerStep:
+class TrainerStep(DroppedStepRedo):
     """One keyframe-parallel training step.  `render_backward(params: dict, keyframe, dL_fn) -> (image, loss)` must
     render the keyframe, call dL_fn(image) -> (loss, dL_dimage) and leave parameter gradients in `grads_flat`."""
 
@@ -205,6 +193,9 @@ class TrainerStep:
                                        single_rank_collectives=single_rank_collectives, grads=grads_flat)
         self.world, self.rank = self.exchange.world, self.exchange.rank
         self.iteration = 0
+        self.engine = None               # the HIP raster engine (on_gpu); None: a backend without an overflow word
+        self._stage = None
+        self._init_step_state()
         # a backend that knows an overflow word (the HIP engine) takes a hook it calls right after its forward
         self._backend_takes_hook = render_backward is not None and "after_forward" in inspect.signature(render_backward).parameters
 
@@ -228,58 +219,22 @@ class TrainerStep:
     def _exchange_sharded(self) -> bool:
         return self.exchange.sharded
 
-    def keyframe_for(self, step: int, n_keyframes: int) -> int:
-        """Deterministic shared schedule: rank r takes keyframe (step * world + r) mod n."""
-        return (step * self.world + self.rank) % n_keyframes
+    def _exchange(self):
+        return self.exchange
 
     def training_once(self, keyframes, gt_images) -> torch.Tensor:
         """Nothing here waits for the device: a pass whose instance count outgrew some rank's resident capacity is dropped by
         every rank on the device (the optimizer is guarded by the all-reduced overflow word and its step count lives there);
         the rank concerned re-sizes its scratch at its next forward.  The dropped iteration is then run again by every rank before
-        the next one (`redo_dropped_steps`), so no optimizer step of the reference's sequence is lost
+        the next one (`redo_dropped_steps`, step_shared.DroppedStepRedo), so no optimizer step of the reference's sequence is lost
         (src/gaussian_mapper.cpp:1027-1030 never skips one).  CONTRACT: the keyframe's and the target's tensors of a call must
         stay unchanged until the next call (or finish()) has returned -- a redo trains on them again."""
-        # An iteration the device dropped is run again -- same keyframe, same iteration number -- as soon as the host resolves that
-        # step's overflow word, which is before the next iteration is queued (ScaffoldTrainerStep.training_once).  One rank: the
-        # engine's own status word.  N > 1: the SUMMED word every rank mirrored to its host after the gradient exchange
-        # (BucketExchange.mirror_flag), so all ranks redo the same iteration together and replicas stay bit-identical.
-        self._redo_if_dropped()
-        self.iteration += 1
-        k = self.keyframe_for(self.iteration - 1, len(keyframes))
-        self._last_iteration = (keyframes[k], gt_images[k], self.iteration)
-        return self._iteration_body(keyframes[k], gt_images[k], self.iteration)
-
-    def _redo_if_dropped(self):
-        prev = getattr(self, "_last_iteration", None)
-        if prev is None or not getattr(self, "redo_dropped_steps", True) or getattr(self, "use_graph", False):
-            return
-        eng = getattr(self, "engine", None)
-        for _ in range(4):
-            if self.world == 1:
-                dropped = eng is not None and eng.resident and not eng.check(raise_on_overflow=False)
-            else:
-                dropped = bool(self.exchange.step_dropped())
-                if eng is not None and eng.resident:
-                    eng.check(raise_on_overflow=False)      # the rank that overflowed re-calibrates in its next forward
-            if not dropped:
-                break
-            self.redone_steps = getattr(self, "redone_steps", 0) + 1
-            self._iteration_body(*prev)
-            if self.world == 1:
-                break                                       # (a re-calibrating forward cannot overflow)
-        else:
-            raise RuntimeError("an iteration kept being dropped by the device")
-        self._last_iteration = None
-
-    def finish(self):
-        """Resolve the LAST iteration's status word and run that iteration again if the device dropped it (training_once only
-        learns of a drop at the next call).  Call once after the last training_once of a run."""
-        self._redo_if_dropped()
+        return self._next_iteration(keyframes, gt_images)
 
     def _iteration_body(self, keyframe, gt, it: int) -> torch.Tensor:
         lrs = self.learning_rates(it)
         ex = self.exchange
-        if getattr(self, "use_graph", False) and not ex.active:
+        if self.use_graph and not ex.active:
             loss = self._training_once_graph(keyframe, gt, lrs)
             if loss is not None:
                 return loss
@@ -291,7 +246,7 @@ class TrainerStep:
             ex.reduce_flag_async(None)
         flag = ex.wait_flag()
         ex.reduce_gradients(self.grads_flat)  # sum over the keyframes of this step
-        if ex.active and getattr(self, "redo_dropped_steps", True):
+        if ex.active and self.redo_dropped_steps:
             ex.mirror_flag()
         self.optimizer.step(self.params_flat, self.grads_flat, lrs, self.P, 1.0 / self.world, exchange=ex, guard=flag)
         ex.gather(self.params_flat)
@@ -302,56 +257,30 @@ class TrainerStep:
         """Replay the iteration from a captured hipGraph (single rank, calibrated resident rasterizer): the keyframe matrices,
         the target image and the learning rates go through staging buffers refreshed before each replay; same kernels, same
         arguments, same order as the eager path."""
-        assert getattr(self, "engine", None) is not None and isinstance(self.optimizer, FusedAdam), "graph mode needs TrainerStep.on_gpu()"
+        assert self.engine is not None and isinstance(self.optimizer, FusedAdam), "graph mode needs TrainerStep.on_gpu()"
         self.use_graph, self._graphs, self._stage, self.graph_replays = bool(on), {}, None, 0
 
     def _training_once_graph(self, keyframe, gt, lrs):
-        from . import _capi
         eng, opt = self.engine, self.optimizer
-        if not eng.resident or eng.capacity <= 0 or not eng.poll() or eng.capacity <= 0:
+        if not self._graph_ready():
             return None
         view, proj, campos, tanx, tany = keyframe
-        dev = self.params_flat.device
         if self._stage is None:
-            self._stage = dict(packed=torch.zeros(35, dtype=torch.float32, device=dev), gt=torch.empty_like(gt),
-                               lr=torch.zeros(16, dtype=torch.float64, device=dev))
+            self._stage = IterationStage(35, gt)
         st = self._stage
+        st.fill((view, proj, campos), gt)
         groups = field_segments(lrs, self.P)
         key = (eng.capacity, eng._bin_r.data_ptr(), float(tanx), float(tany), tuple(gt.shape))
-        pk = st["packed"]
-        pk[0:16].copy_(view.reshape(-1)); pk[16:32].copy_(proj.reshape(-1)); pk[32:35].copy_(campos.reshape(-1))
-        st["gt"].copy_(gt)
-        vals = (C.c_double * len(groups))(*[float(g[2]) for g in groups])
-        stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        _capi.check(_capi.lib().segs_set_doubles(p(st["lr"]), vals, len(groups), stream()), "segs_set_doubles")
-        opt.count.sync_device_calls()
-        g = self._graphs.get(key)
-        if g is None:
+
+        def body():
+            pk = st.packed
             skf = (pk[0:16].view(4, 4), pk[16:32].view(4, 4), pk[32:35], tanx, tany)
-            guard = eng._status[3:4]
-            segs = (_capi.AdamSegment * len(groups))()
-            for i, (o, n, _) in enumerate(groups):
-                segs[i].offset, segs[i].count, segs[i].lr = o, n, 0.0
+            self.render_backward(self.params, skf, lambda im: self.loss_and_grad(im, st.gt))
+            adam_step((self.params_flat, self.grads_flat, opt.exp_avg, opt.exp_avg_sq), groups, opt.opt, opt.count,
+                      ptr(eng.overflow_word()), self.params_flat.device, staged_lr=st.lr_ptr())
 
-            def body():
-                self.render_backward(self.params, skf, lambda im: self.loss_and_grad(im, st["gt"]))
-                rc = _capi.lib().segs_adam_step_graph(p(self.params_flat), p(self.grads_flat), p(opt.exp_avg), p(opt.exp_avg_sq), segs,
-                                                      len(groups), p(st["lr"]), opt.opt.beta1, opt.opt.beta2, opt.opt.eps, p(opt.count.words),
-                                                      1.0, 1, p(guard), stream())
-                _capi.check(rc, "segs_adam_step_graph")
-
-            eng.check(raise_on_overflow=False)
-            if eng.capacity <= 0:
-                return None
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                body()
-            self._graphs = {key: g}
-        g.replay()
-        opt.count.calls += 1
-        eng.after_graph_replay()
-        self.graph_replays += 1
+        if not self._replay_iteration(st, groups, (opt.count,), key, 0, lambda: body):   # one graph: a new key replaces it
+            return None
         return self.fused_loss.out[0]
 
     # ---- product wiring -------------------------------------------------------------------------------
@@ -378,8 +307,7 @@ class TrainerStep:
             image = eng.forward(bg, params["means3D"], params["colors"], params["opacity"], params["scales"],
                                 params["rotations"], view, proj, campos, tanx, tany)
             if after_forward is not None:
-                status = getattr(eng, "_status", None)
-                after_forward(status[3:4] if (status is not None and eng._last_resident) else None)
+                after_forward(eng.overflow_word())
             loss, dL = dL_fn(image)
             eng.backward(dL)
             return loss

@@ -13,7 +13,7 @@ of the keyframe-parallel all-reduce.  `_opacity` and `_rotation` (groups 3, 5) n
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -22,6 +22,7 @@ import torch.distributed as dist
 from . import _capi
 from .gaussian_trainer import DeviceStepCount, FusedL1SSIM, expon_lr
 from .raster_engine import RasterEngine
+from .step_shared import DroppedStepRedo, IterationStage, adam_step, ptr as _p, stream_ptr
 
 
 @dataclass
@@ -94,9 +95,6 @@ class ScaffoldOptimizationParams:
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-15
-
-
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
 
 
 class ScaffoldModel:
@@ -243,7 +241,7 @@ class NeuralGaussians:
                                 device=model.device)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.model.device).cuda_stream)
+        return stream_ptr(self.model.device)
 
     def forward(self, camera_center: torch.Tensor, pose7: torch.Tensor, visible_radii: Optional[torch.Tensor]):
         m = self.model
@@ -313,14 +311,14 @@ class Keyframe:
     pose7: torch.Tensor      # (t_xyz, q_wxyz), gaussian_renderer.cpp:258-261
     tanfovx: float
     tanfovy: float
+    _packed: Optional[torch.Tensor] = field(default=None, init=False, repr=False, compare=False)
 
     def packed(self) -> torch.Tensor:
         """view | proj | campos | pose7 as one 42-float device tensor (made once): one copy refreshes a captured iteration's
         staging keyframe."""
-        pk = getattr(self, "_packed", None)
-        if pk is None:
-            pk = self._packed = torch.cat([self.view.reshape(-1), self.proj.reshape(-1), self.campos.reshape(-1), self.pose7.reshape(-1)]).contiguous()
-        return pk
+        if self._packed is None:
+            self._packed = torch.cat([self.view.reshape(-1), self.proj.reshape(-1), self.campos.reshape(-1), self.pose7.reshape(-1)]).contiguous()
+        return self._packed
 
     @classmethod
     def from_pose(cls, q_wxyz, t_xyz, width: int, height: int, fx: float, fy: float, device, znear: float = 0.01,
@@ -345,7 +343,7 @@ class Keyframe:
                    cam.tanfovy)
 
 
-class ScaffoldTrainerStep:
+class ScaffoldTrainerStep(DroppedStepRedo):
     """prefilter_voxel -> generate_neural_gaussians -> rasterize -> L1/SSIM -> backward -> [all-reduce] -> fused Adam,
     all on the device without a host synchronisation in steady state."""
 
@@ -401,7 +399,6 @@ class ScaffoldTrainerStep:
         self.single_rank_collectives = False   # keyframe_parallel.BucketExchange: run the collectives with one rank too
         self.densifier = None            # densify.AnchorDensifier, see enable_densification()
         self.densify_generator = None
-        self.keyframe_selector = None    # keyframe_window.SlidingWindowKeyframes: the mapper's walk instead of round-robin
         # the mapper (not the trainer) multiplies rendering and target by mask_rgb = (gt != 0).any(-1): gt is (3,H,W), so this
         # is a per-(channel, row) mask of shape (3,H,1) that blanks rows whose target is entirely zero
         # (src/gaussian_mapper.cpp:917-922).  Off by default (trainer semantics); mapper_config.make_mapper_step turns it on.
@@ -417,13 +414,9 @@ class ScaffoldTrainerStep:
         # the device drops an iteration whose forward overflowed the resident capacity; with one rank the host runs it again
         # before the next one (training_once), so no optimizer step of the reference's sequence is lost
         # (`pose_grads` of an iteration the device dropped are meaningless, like its loss: the redo refills them)
-        self.redo_dropped_steps = True
-        self.redone_steps = 0
-        self._last_iteration = None
-        self.use_graph = False
-        self._graphs = {}
+        self._init_step_state()
         self._graph_stage = {}
-        self.graph_replays = 0
+        self._rot_key = self._ex = None
 
     def _make_engine(self, P: int, width: int, height: int) -> RasterEngine:
         return RasterEngine(P, width, height, self.model.device, resident=True, skip_nonpositive_opacity=True,
@@ -473,21 +466,30 @@ class ScaffoldTrainerStep:
         fr, it = self.freq_reg, self.iteration
         return (it < fr["until"] and fr["lambda_low"] != 0.0, fr["start"] < it < fr["until"] and fr["lambda_high"] != 0.0)
 
-    def _freq_fused_add(self, image: torch.Tensor, gt: torch.Tensor, dL: torch.Tensor, loss_word: torch.Tensor) -> bool:
-        """Adds the regulariser's gradient to dL and its value to loss_word, both in place; False when it is off."""
+    def _freq_fused_for(self, low_on: bool, high_on: bool):
+        """The FusedFrequencyLoss of the level in flight with these terms on (made on first use)."""
         from .frequency_loss import FusedFrequencyLoss
         fr = self.freq_reg
-        low_on, high_on = self._freq_active()
-        if not (low_on or high_on):
-            return False
         key = (self.W, self.H, low_on, high_on)
         fl = self._freq_fused.get(key)
         if fl is None:
             fl = self._freq_fused[key] = FusedFrequencyLoss(
                 self.H, self.W, self.model.device, lambda_high=fr["lambda_high"] if high_on else 0.0, scales=fr["scales"],
                 multi_resolution=fr["multi"], lambda_low=fr["lambda_low"] if low_on else 0.0)
-        fl(image, gt, dL, loss_word)
-        return True
+        return fl
+
+    def _freq_term(self, image: torch.Tensor, gt: torch.Tensor, loss: torch.Tensor, dL: torch.Tensor):
+        """(loss, dL) with the frequency regulariser of this iteration added (nothing while its window is closed)."""
+        if self.freq_reg["fused"]:
+            # loss is element 0 of the fused L1/SSIM object's result words, dL its own gradient buffer: both updated in place
+            low_on, high_on = self._freq_active()
+            if low_on or high_on:
+                self._freq_fused_for(low_on, high_on)(image, gt, dL, loss.view(1))
+        else:
+            floss, fg = self._freq_grad(image, gt)
+            if fg is not None:
+                dL, loss = dL + fg, loss + floss
+        return loss, dL
 
     def _freq_grad(self, image: torch.Tensor, gt: torch.Tensor):
         from . import loss_utils
@@ -512,23 +514,23 @@ class ScaffoldTrainerStep:
         self.densify_generator = torch.Generator(device="cpu").manual_seed(seed)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.model.device).cuda_stream)
+        return stream_ptr(self.model.device)
 
     def _adam(self, groups, count: "DeviceStepCount", guard):
         """Fused Adam over `groups` (restricted to this rank's shard of the bucket when the optimizer is sharded), guarded by
         the summed overflow word, step count on the device."""
-        groups = self._exchange().clip_segments(groups)
-        call = count.eager_call()        # the launch below always happens (an empty shard still advances the count)
-        if not groups:
-            groups = [(0, 0, 0.0)]
-        segs = (_capi.AdamSegment * len(groups))()
-        for i, (o, n, lr) in enumerate(groups):
-            segs[i].offset, segs[i].count, segs[i].lr = o, n, float(lr)
         m = self.model
-        st = self._lib.segs_adam_step_device(_p(m.params), _p(m.grads), _p(m.exp_avg), _p(m.exp_avg_sq), segs, len(groups),
-                                             self.opt.beta1, self.opt.beta2, self.opt.eps, _p(count.words), call,
-                                             1.0 / self.world, 1, guard, self._stream())
-        _capi.check(st, "segs_adam_step_device")
+        adam_step((m.params, m.grads, m.exp_avg, m.exp_avg_sq), self._exchange().clip_segments(groups), self.opt, count, guard,
+                  m.device, 1.0 / self.world)
+
+    def _adam_parts(self, groups, skip_anchors: bool = False):
+        """(index of the first group, groups, step count) per Adam launch of an iteration: one over everything until the first
+        densification, then the anchor groups and the MLPs under their own counts (`skip_anchors`: the MLPs alone)."""
+        if skip_anchors:
+            return [(4, groups[4:], self._mlp_count)]
+        if self._anchor_count is None:
+            return [(0, groups, self._mlp_count)]
+        return [(0, groups[:4], self._anchor_count), (4, groups[4:], self._mlp_count)]
 
     def learning_rates(self, it: int) -> Dict[str, float]:
         """updateLearningRate (src/gaussian_model.cpp:874-915); anchor/offset scaled by spatial_lr_scale (:637,640)."""
@@ -551,7 +553,7 @@ class ScaffoldTrainerStep:
         only when densification rewrote rows."""
         m = self.model
         key = (m.A, m.rotation._version, m.rotation.data_ptr())
-        if getattr(self, "_rot_key", None) != key:
+        if self._rot_key != key:
             self._rot_key, self._rot_normalized = key, torch.nn.functional.normalize(m.rotation[:m.A]).contiguous()
         return self._rot_normalized
 
@@ -583,6 +585,10 @@ class ScaffoldTrainerStep:
         self._depth_fn()
 
     def render(self, kf: Keyframe) -> torch.Tensor:
+        return self._render(kf)
+
+    def _render(self, kf: Keyframe, mark=None) -> torch.Tensor:
+        """render().  `mark(i)`: profile_phases' phase boundaries 0 (before the prefilter), 1 and 2 (around the neural forward)."""
         ng = self.neural
         if self.model.capacity * self.model.dims.n_offsets > self.engine.P:   # the map outgrew the engines' buffers
             self.engine = self._make_engine(self.model.capacity * self.model.dims.n_offsets, self.W, self.H)
@@ -591,20 +597,27 @@ class ScaffoldTrainerStep:
         self.engine.set_active(ng.P)
         if self.fuse_projection:
             self.engine.check(raise_on_overflow=False)   # an overflow of the previous step sends this one through the calibrating path
-        if self.fuse_projection and self.engine.can_take_projected():
-            # the neural forward projects the candidates itself; the rasterizer starts at the binning
-            # (and works out prefilter_voxel's radii on the way: self.visible_radii is filled by the same call)
+        fused = self.fuse_projection and self.engine.can_take_projected()
+        if mark: mark(0)  # noqa: E701
+        # fused: the neural forward projects the candidates itself and the rasterizer starts at the binning;
+        # prefilter_voxel's radii come out of the same call (self.visible_radii), so both then count as neural_forward
+        radii = None if fused else self.prefilter_voxel(kf)
+        if mark: mark(1)  # noqa: E701
+        if fused:
             ng.forward_projected(kf, self.visible_radii, self.engine, anchor_rotations=self._anchor_rotations())
+            if mark: mark(2)  # noqa: E701
             return self.engine.forward_projected(self.bg, ng.means3D, ng.scales, ng.rotations, kf.view, kf.proj, kf.campos,
                                                  kf.tanfovx, kf.tanfovy)
-        ng.forward(kf.campos, kf.pose7, self.prefilter_voxel(kf))
+        ng.forward(kf.campos, kf.pose7, radii)
+        if mark: mark(2)  # noqa: E701
         return self.engine.forward(self.bg, ng.means3D, ng.colors, ng.opacity, ng.scales, ng.rotations, kf.view, kf.proj,
                                    kf.campos, kf.tanfovx, kf.tanfovy)
 
-    def _forward_backward(self, kf: Keyframe, gt: torch.Tensor, exchange=None, flag_on_host: bool = False, depth=None):
+    def _forward_backward(self, kf: Keyframe, gt: torch.Tensor, exchange=None, flag_on_host: bool = False, depth=None, mark=None):
         """`flag_on_host`: the caller reads the summed overflow word on the host before the gradient exchange (adjust_anchor
         iterations), so it needs its own collective instead of riding with the gradients.  `depth`: the keyframe's sensor depth
-        (tensor or depth_loss.DepthTarget) on a step made with depth_loss; None = a colour-only iteration."""
+        (tensor or depth_loss.DepthTarget) on a step made with depth_loss; None = a colour-only iteration.  `mark`: see
+        _iteration_sequence."""
         self.use_level(gt.shape[-1], gt.shape[-2])
         self.depth_terms = None
         if self.model.A == 0:
@@ -614,29 +627,34 @@ class ScaffoldTrainerStep:
                 exchange.reduce_flag_async(None, allow_piggyback=not flag_on_host)
             self.pose_grads = None
             return self.loss_fn(torch.zeros(3, self.H, self.W, device=self.model.device), gt)[0]
-        image = self.render(kf)
+        return self._iteration_sequence(kf, gt, self._freq_term if self.freq_reg is not None else None, exchange, not flag_on_host,
+                                        self._row_mask_of if self.row_mask else None, depth, mark)
+
+    def _iteration_sequence(self, kf: Keyframe, gt: torch.Tensor, freq_term=None, exchange=None, piggyback: bool = True,
+                            mask_of=None, depth=None, mark=None):
+        """THE order of an iteration up to the gradients in model.grads: prefilter -> neural forward -> raster forward -> loss ->
+        frequency term -> raster backward -> neural backward (the first three inside _render).  Its users supply what differs:
+        _forward_backward the exchange whose flag reduction starts after the forward, the row mask (`mask_of`), the depth term
+        and _freq_term; the captured iteration a staged keyframe and target and a `freq_term(image, gt, loss, dL) -> (loss, dL)`
+        fed from the staged target tables; profile_phases `mark(i)`, called at phase boundary i = 0..7 (HIP events; costs
+        nothing when absent)."""
+        image = self._render(kf, mark)
+        if mark: mark(3)  # noqa: E701
         if exchange is not None:
             # the overflow word is final once the forward's binning has run: its all-reduce hides behind loss and backward
-            status = getattr(self.engine, "_status", None)
-            exchange.reduce_flag_async(status[3:4] if (status is not None and self.engine._last_resident) else None,
-                                       allow_piggyback=not flag_on_host)
+            exchange.reduce_flag_async(self.engine.overflow_word(), allow_piggyback=piggyback)
         mask = None
-        if self.row_mask:
-            mask, gt = self._row_mask_of(gt)
+        if mask_of is not None:
+            mask, gt = mask_of(gt)
             if mask is not None:
                 image = image * mask
         loss, dL = self.loss_fn(image, gt)
-        if self.freq_reg is not None:
-            if self.freq_reg["fused"]:
-                # loss is element 0 of the fused L1/SSIM object's result words, dL its own gradient buffer: both updated in place
-                self._freq_fused_add(image, gt, dL, loss.view(1))
-            else:
-                floss, fg = self._freq_grad(image, gt)
-                if fg is not None:
-                    dL = dL + fg
-                    loss = loss + floss
+        if mark: mark(4)  # noqa: E701
+        if freq_term is not None:
+            loss, dL = freq_term(image, gt, loss, dL)
         if mask is not None:
             dL = dL * mask
+        if mark: mark(5)  # noqa: E701
         if depth is not None:
             # after the colour loss and the regulariser, into the same loss word; the row mask is a colour-only matter
             dfn = self._depth_fn()
@@ -645,8 +663,10 @@ class ScaffoldTrainerStep:
             g = self.engine.backward(dL, dL_ddepth, dL_dalpha)
         else:
             g = self.engine.backward(dL)            # the call of a step without depth supervision, as it was
+        if mark: mark(6)  # noqa: E701
         self.neural.backward(g["means3D"], g["colors"], g["opacity"], g["scales"], g["rotations"], self.scaling_reg_weight,
                              camera_grad=self.pose_grad)
+        if mark: mark(7)  # noqa: E701
         if self.pose_grad:
             # views of the current level's device buffers: valid until the next iteration, no host synchronisation
             self.pose_grads = {"viewmatrix": self.engine.dL_dviewmatrix, "projmatrix": self.engine.dL_dprojmatrix,
@@ -735,9 +755,6 @@ class ScaffoldTrainerStep:
             self._row_mask_cache[key] = hit
         return hit
 
-    def keyframe_for(self, step: int, n_keyframes: int) -> int:
-        return (step * self.world + self.rank) % n_keyframes
-
     def training_once(self, keyframes: List[Keyframe], gt_images: List[torch.Tensor], gt_depths=None) -> torch.Tensor:
         """One mapper iteration.  `gt_depths` (step made with depth_loss): one sensor depth per keyframe -- a tensor, a prepared
         depth_loss.DepthTarget, or None for a colour-only iteration on that keyframe.
@@ -763,41 +780,7 @@ class ScaffoldTrainerStep:
         if gt_depths is not None:
             for g_, d_ in zip(gt_images, gt_depths):
                 self._check_depth(g_, d_)
-        self._redo_if_dropped()
-        self.iteration += 1
-        if self.keyframe_selector is not None:
-            # useOneRandomSlidingWindowKeyframe (src/gaussian_mapper.cpp:827): one draw per rank, identical on every rank
-            k = self.keyframe_selector.use_for_ranks(self.world)[self.rank]
-        else:
-            k = self.keyframe_for(self.iteration - 1, len(keyframes))
-        depth = None if gt_depths is None else gt_depths[k]
-        self._last_iteration = (keyframes[k], gt_images[k], self.iteration, depth)
-        return self._iteration_body(keyframes[k], gt_images[k], self.iteration, depth)
-
-    def _redo_if_dropped(self):
-        prev = self._last_iteration
-        if prev is None or not self.redo_dropped_steps or self.use_graph or not self.engine.resident:
-            return
-        for _ in range(4):
-            if self.world == 1:
-                dropped = not self.engine.check(raise_on_overflow=False)
-            else:
-                dropped = bool(self._exchange().step_dropped())
-                self.engine.check(raise_on_overflow=False)       # the rank that overflowed re-calibrates in its next forward
-            if not dropped:
-                break
-            self.redone_steps += 1
-            self._iteration_body(*prev)
-            if self.world == 1:
-                break                                            # (a re-calibrating forward cannot overflow)
-        else:
-            raise RuntimeError("an iteration kept being dropped by the device")
-        self._last_iteration = None
-
-    def finish(self):
-        """Resolve the LAST iteration's overflow word and run that iteration again if the device dropped it (training_once only
-        learns of a drop at the next call).  Call once after the last training_once of a run, before reporting."""
-        self._redo_if_dropped()
+        return self._next_iteration(keyframes, gt_images, gt_depths)
 
     def lost_steps(self) -> int:
         """Iterations the device dropped and nobody ran again (0 with redo_dropped_steps after finish(); synchronises)."""
@@ -828,7 +811,7 @@ class ScaffoldTrainerStep:
                 flag = ex.wait_flag()
             else:
                 raise RuntimeError("resident rasterizer kept overflowing its re-sized scratch")
-        guard = C.c_void_p(flag.data_ptr())
+        guard = _p(flag)
         # A densification may re-size the bucket (reserve() moves the MLP block), so the shard partition the optimizer clips
         # to below is not the one a reduce-scatter would have summed for: every element gets the full sum on those steps.
         ex.reduce_gradients(self.model.grads, dense=adjust_now)
@@ -847,7 +830,6 @@ class ScaffoldTrainerStep:
                 adjusted = True
                 ex = self._exchange()      # the bucket may have been re-sized: new shard ranges (the moments are whole here)
         groups = self.model.adam_groups(lrs)
-        anchor_groups, mlp_groups = groups[:4], groups[4:]
         if adjusted:
             # the six anchor tensors were re-created by adjust_anchor: no gradient, skipped by Adam this iteration
             # (src/gaussian_model.cpp:1677), so from here on their step count lags the MLPs'
@@ -855,12 +837,8 @@ class ScaffoldTrainerStep:
                 self.model.grad(name).zero_()
             if self._anchor_count is None:
                 self._anchor_count = self._mlp_count.clone()
-            self._adam(mlp_groups, self._mlp_count, guard)
-        elif self._anchor_count is None:
-            self._adam(groups, self._mlp_count, guard)
-        else:
-            self._adam(anchor_groups, self._anchor_count, guard)
-            self._adam(mlp_groups, self._mlp_count, guard)
+        for _, part, count in self._adam_parts(groups, skip_anchors=adjusted):
+            self._adam(part, count, guard)
         if ex.sharded:
             ex.gather(self.model.params)
             self.model.grads.zero_()      # outside this rank's shard the bucket still holds its own contribution
@@ -879,27 +857,12 @@ class ScaffoldTrainerStep:
         self.use_graph = bool(on)
         self._graphs.clear()
 
-    def _graph_stage_for(self, fl):
-        key = (self.W, self.H)
-        st = self._graph_stage.get(key)
-        if st is None:
-            dev = self.model.device
-            pk = torch.zeros(42, dtype=torch.float32, device=dev)
-            st = dict(packed=pk, gt=torch.empty((3, self.H, self.W), dtype=torch.float32, device=dev),
-                      lr=torch.zeros(16, dtype=torch.float64, device=dev), table=None)
-            self._graph_stage[key] = st
-        if fl is not None and (st["table"] is None or st["table"].numel() != fl._target_floats):
-            st["table"] = torch.empty(fl._target_floats, dtype=torch.float32, device=self.model.device)
-        return st
-
     def _training_once_graph(self, kf: Keyframe, gt: torch.Tensor, lrs, in_stat_window: bool):
         """One iteration from the captured graph; None when this iteration has to take the eager path."""
         self.use_level(gt.shape[-1], gt.shape[-2])
         eng, m = self.engine, self.model
-        if m.A == 0 or not eng.resident or eng.capacity <= 0 or not eng.poll() or eng.capacity <= 0:
-            return None                                  # not calibrated (or an overflow just came to light): eager, which re-sizes
-        if m.capacity * m.dims.n_offsets > eng.P:
-            return None
+        if m.A == 0 or not self._graph_ready() or m.capacity * m.dims.n_offsets > eng.P:
+            return None                                  # not calibrated, or outgrown: eager, which re-sizes
         if self.row_mask and self._row_mask_of(gt)[0] is not None:
             return None                                  # a target with blanked rows multiplies image and gradient by its mask: eager
         fl = None
@@ -908,130 +871,65 @@ class ScaffoldTrainerStep:
             if low_on or (high_on and not self.freq_reg["fused"]):
                 return None
             if high_on:
-                from .frequency_loss import FusedFrequencyLoss
-                fr = self.freq_reg
-                fkey = (self.W, self.H, False, True)
-                fl = self._freq_fused.get(fkey)
-                if fl is None:
-                    fl = self._freq_fused[fkey] = FusedFrequencyLoss(self.H, self.W, m.device, lambda_high=fr["lambda_high"], scales=fr["scales"],
-                                                                      multi_resolution=fr["multi"])
-        st = self._graph_stage_for(fl)
+                fl = self._freq_fused_for(False, True)
+        st = self._graph_stage.get((self.W, self.H))
+        if st is None:
+            st = self._graph_stage[(self.W, self.H)] = IterationStage(42, gt)
+        if fl is not None and (st.table is None or st.table.numel() != fl._target_floats):
+            st.table = torch.empty(fl._target_floats, dtype=torch.float32, device=m.device)
         groups = m.adam_groups(lrs)
-        split = self._anchor_count is not None
+        parts = self._adam_parts(groups)
         key = (self.W, self.H, m.A, m.capacity, id(eng), eng.capacity, eng._bin_r.data_ptr(), float(kf.tanfovx), float(kf.tanfovy),
-               bool(in_stat_window), fl is not None, split, len(groups), m.params.data_ptr(), bool(self.fuse_projection))
+               bool(in_stat_window), fl is not None, len(parts), len(groups), m.params.data_ptr(), bool(self.fuse_projection))
         # ---- refresh the staging buffers (ordinary stream work in front of the replay)
-        st["packed"].copy_(kf.packed())
-        st["gt"].copy_(gt)
+        st.fill((kf.packed(),), gt)
         if fl is not None:
-            st["table"].copy_(fl.target_block(gt))
-        vals = (C.c_double * len(groups))(*[float(g[2]) for g in groups])
-        _capi.check(self._lib.segs_set_doubles(_p(st["lr"]), vals, len(groups), self._stream()), "segs_set_doubles")
-        counts = (self._anchor_count, self._mlp_count) if split else (self._mlp_count,)
-        for c in counts:
-            c.sync_device_calls()
-        g = self._graphs.get(key)
-        if g is None:
-            if len(self._graphs) > 16:
-                self._graphs.clear()
-            pk = st["packed"]
-            skf = Keyframe(pk[0:16].view(4, 4), pk[16:32].view(4, 4), pk[32:35], pk[35:42], kf.tanfovx, kf.tanfovy)
-            status = eng._status
-            guard = C.c_void_p(status[3:4].data_ptr())
-            d = self.densifier
-            seg_all = [(o, n) for o, n, _ in groups]
+            st.table.copy_(fl.target_block(gt))
 
-            def adam(seg, lr_off, count):
-                segs = (_capi.AdamSegment * len(seg))()
-                for i, (o, n) in enumerate(seg):
-                    segs[i].offset, segs[i].count, segs[i].lr = o, n, 0.0
-                lr_ptr = C.c_void_p(st["lr"].data_ptr() + 8 * lr_off)
-                rc = self._lib.segs_adam_step_graph(_p(m.params), _p(m.grads), _p(m.exp_avg), _p(m.exp_avg_sq), segs, len(seg), lr_ptr,
-                                                    self.opt.beta1, self.opt.beta2, self.opt.eps, _p(count.words), 1.0, 1, guard, self._stream())
-                _capi.check(rc, "segs_adam_step_graph")
+        def make_body():
+            pk = st.packed
+            skf = Keyframe(pk[0:16].view(4, 4), pk[16:32].view(4, 4), pk[32:35], pk[35:42], kf.tanfovx, kf.tanfovy)
+
+            def staged_freq(image, _gt, loss, dL):
+                fl.apply(image, st.table, dL, loss.view(1))
+                return loss, dL
 
             def body():
-                image = self.render(skf)
-                loss, dL = self.loss_fn(image, st["gt"])
-                if fl is not None:
-                    fl.apply(image, st["table"], dL, loss.view(1))
-                gr = eng.backward(dL)
-                self.neural.backward(gr["means3D"], gr["colors"], gr["opacity"], gr["scales"], gr["rotations"], self.scaling_reg_weight)
+                self._iteration_sequence(skf, st.gt, staged_freq if fl is not None else None)
+                guard = _p(eng.overflow_word())
                 if in_stat_window:
-                    d.training_statis(self.neural, self.visible_radii, eng.radii, eng.dL_dmean2D, guard, into_delta=False)
-                if split:
-                    adam(seg_all[:4], 0, self._anchor_count)
-                    adam(seg_all[4:], 4, self._mlp_count)
-                else:
-                    adam(seg_all, 0, self._mlp_count)
+                    self.densifier.training_statis(self.neural, self.visible_radii, eng.radii, eng.dL_dmean2D, guard, into_delta=False)
+                for first, part, count in parts:
+                    adam_step((m.params, m.grads, m.exp_avg, m.exp_avg_sq), part, self.opt, count, guard, m.device,
+                              staged_lr=st.lr_ptr(first))
 
-            eng.check(raise_on_overflow=False)           # nothing pending while the capture runs
-            if eng.capacity <= 0:
-                return None
             if fl is not None and not getattr(fl, "_ran_eagerly", False):
                 # the FFT library sets a transform up on its first execution: not inside a capture
-                fl.apply(eng.out_color, st["table"], torch.zeros_like(st["gt"]))
+                fl.apply(eng.out_color, st.table, torch.zeros_like(st.gt))
                 fl._ran_eagerly = True
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                body()
-            self._graphs[key] = g
-        g.replay()
-        for c in counts:
-            c.calls += 1                                 # (the device-side call count advanced with the replay)
-        eng.after_graph_replay()
-        self.graph_replays += 1
+            return body
+
+        if not self._replay_iteration(st, groups, [count for _, _, count in parts], key, 16, make_body):
+            return None
         return self.loss_fn.out[0]
 
     def profile_phases(self, kf: Keyframe, gt: torch.Tensor, iters: int = 20) -> Dict[str, float]:
-        """Mean milliseconds per phase of one iteration (HIP events on the current stream between the same calls
-        training_once issues; measurement support for bench.py, single rank, no densification)."""
+        """Mean milliseconds per phase of one iteration: HIP events on the current stream at the phase boundaries of
+        _iteration_sequence, then the Adam launches of _iteration_body (measurement support for bench.py; single rank, no
+        exchange, no densification, unguarded Adam).  The iteration is training_once's own, taken through _forward_backward:
+        on a plain step (no row mask, no pose gradient, no depth) that is the launch sequence this method always issued; on
+        any other step -- pyramid levels, row mask, camera forms, a map that outgrew the engine -- it does what training_once
+        does for that step (colour-only: it takes no sensor depth)."""
         names = ("prefilter_voxel", "neural_forward", "raster_forward", "loss", "freq_loss", "raster_backward", "neural_backward",
                  "adam")
         tot = {n: 0.0 for n in names}
-        ng = self.neural
         for _ in range(iters):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
             self.iteration += 1
             lrs = self.learning_rates(self.iteration)
-            self.engine.set_active(ng.P)
-            if self.fuse_projection:
-                self.engine.check(raise_on_overflow=False)
-            fused = self.fuse_projection and self.engine.can_take_projected()
-            ev[0].record()
-            radii = None if fused else self.prefilter_voxel(kf)
-            ev[1].record()
-            if fused:
-                # (prefilter and per-Gaussian projection then count as neural_forward: they run inside its kernels)
-                ng.forward_projected(kf, self.visible_radii, self.engine, anchor_rotations=self._anchor_rotations())
-                ev[2].record()
-                image = self.engine.forward_projected(self.bg, ng.means3D, ng.scales, ng.rotations, kf.view, kf.proj, kf.campos,
-                                                      kf.tanfovx, kf.tanfovy)
-            else:
-                ng.forward(kf.campos, kf.pose7, radii)
-                ev[2].record()
-                image = self.engine.forward(self.bg, ng.means3D, ng.colors, ng.opacity, ng.scales, ng.rotations, kf.view, kf.proj,
-                                            kf.campos, kf.tanfovx, kf.tanfovy)
-            ev[3].record()
-            loss, dL = self.loss_fn(image, gt)
-            ev[4].record()
-            if self.freq_reg is not None:       # the mapper's frequency regulariser, when its iteration window is open
-                if self.freq_reg["fused"]:
-                    self._freq_fused_add(image, gt, dL, loss.view(1))
-                else:
-                    _, fg = self._freq_grad(image, gt)
-                    dL = dL if fg is None else dL + fg
-            ev[5].record()
-            g = self.engine.backward(dL)
-            ev[6].record()
-            ng.backward(g["means3D"], g["colors"], g["opacity"], g["scales"], g["rotations"], self.scaling_reg_weight)
-            ev[7].record()
-            groups = self.model.adam_groups(lrs)
-            if self._anchor_count is None:
-                self._adam(groups, self._mlp_count, None)
-            else:
-                self._adam(groups[:4], self._anchor_count, None)
-                self._adam(groups[4:], self._mlp_count, None)
+            self._forward_backward(kf, gt, mark=lambda i: ev[i].record())
+            for _, part, count in self._adam_parts(self.model.adam_groups(lrs)):
+                self._adam(part, count, None)
             ev[8].record()
             torch.cuda.synchronize(self.model.device)
             for i, n in enumerate(names):
@@ -1049,7 +947,7 @@ class ScaffoldTrainerStep:
     def _exchange(self):
         """The step's BucketExchange over the model's flat bucket (rebuilt when densification re-sized the bucket)."""
         from .keyframe_parallel import BucketExchange
-        ex = getattr(self, "_ex", None)
+        ex = self._ex
         total = self.model.params.numel()
         # Frozen anchor positions (Optimization.position_lr_init = position_lr_final = 0: the Replica and TUM configurations,
         # SURVEY 5.6) head the bucket and nobody ever applies their gradient: they stay out of the exchange -- 3 of the 71

@@ -169,6 +169,11 @@ class RasterEngine:
             self._status_pending = True
         self._last_resident = True
 
+    def overflow_word(self):
+        """The overflow word of the last forward (a 1-element int32 device view; non-zero: that pass is invalid), or None if that
+        forward was not resident."""
+        return self._status[3:4] if self._last_resident else None
+
     def after_graph_replay(self):
         """Bookkeeping of a resident forward + backward that ran from a captured graph (the Python side of forward() did not)."""
         self._status_issued()

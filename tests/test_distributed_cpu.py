@@ -124,6 +124,23 @@ def test_two_rank_step_matches_summed_gradients(tmp_path, sharded):
     assert np.array_equal(flat.numpy(), p0)
 
 
+def test_fresh_trainer_step_owns_its_redo_state_and_finish_is_a_no_op():
+    """A step nobody has called yet has every attribute the redo path reads (no getattr defaults), and nothing to run again."""
+    from segs_slam_amd.gaussian_trainer import OptimizationParams, TorchAdam, TrainerStep
+    sc, _, _ = _make()
+    flat = _params(sc)
+    grads = torch.zeros_like(flat)
+    opt = OptimizationParams()
+    adam = TorchAdam(flat.numel(), "cpu", opt)
+    step = TrainerStep(flat, sc.P, _oracle_backend(sc, grads, sc.P), adam, opt, grads)
+    own = vars(step)
+    assert own["redo_dropped_steps"] is True and own["redone_steps"] == 0 and own["use_graph"] is False and own["engine"] is None
+    before = flat.clone()
+    step.finish()
+    assert torch.equal(flat, before) and float(grads.abs().max()) == 0.0
+    assert step.iteration == 0 and adam.step_count == 0 and step.redone_steps == 0
+
+
 def test_expon_lr_and_schedule():
     from segs_slam_amd.gaussian_trainer import expon_lr
     assert abs(expon_lr(0, 1.6e-4, 1.6e-6, 30000) - 1.6e-4) < 1e-12

@@ -93,6 +93,55 @@ def test_scaffold_graph_forward_is_bit_identical_and_learning_rates_follow():
     assert step_g.graph_replays >= 4
 
 
+PHASES = ("prefilter_voxel", "neural_forward", "raster_forward", "loss", "freq_loss", "raster_backward", "neural_backward", "adam")
+
+
+@pytest.mark.parametrize("start_iteration", [0, 10_000])       # without / with the frequency regulariser's window open
+def test_profile_phases_runs_the_iteration_training_once_runs(start_iteration):
+    """profile_phases takes the iteration through the same sequence as training_once: from identical parameters and moments
+    one profiled iteration renders the same image bit for bit (the forward has no atomics), leaves the same loss word and
+    counters, and its update agrees entry by entry within the bound of the eager-against-replay test above."""
+    step_t, kfs, gts = _scaffold(11, False, densify=False)
+    step_p, _, _ = _scaffold(11, False, densify=False)
+    kf, gt = kfs[0], gts[0]
+    for s in (step_t, step_p):                  # calibrate the resident rasterizer
+        for _ in range(2):
+            s.training_once([kf], [gt])
+        s.finish()
+    for name in ("params", "exp_avg", "exp_avg_sq"):
+        getattr(step_p.model, name).copy_(getattr(step_t.model, name))
+    step_t.iteration = step_p.iteration = start_iteration
+    p_before = step_t.model.params.clone()
+    step_t.training_once([kf], [gt])
+    phases = step_p.profile_phases(kf, gt, iters=1)
+    torch.cuda.synchronize()
+    assert torch.equal(step_t.engine.out_color, step_p.engine.out_color)
+    assert float(step_t.loss_fn.out[0]) == float(step_p.loss_fn.out[0])
+    assert step_t.iteration == step_p.iteration == start_iteration + 1
+    assert step_t._mlp_count.value() == step_p._mlp_count.value() == 3
+    upd_t, upd_p = (step_t.model.params - p_before).cpu().numpy(), (step_p.model.params - p_before).cpu().numpy()
+    bad = np.abs(upd_p - upd_t) > 2e-3 * np.abs(upd_t) + 1e-6
+    assert (np.abs(upd_t) > 0).mean() > 0.05 and bad.mean() < 1e-2, float(bad.mean())
+    assert tuple(phases) == PHASES
+    assert all(np.isfinite(v) and v >= 0 for v in phases.values()), phases
+
+
+def test_profile_phases_remakes_an_engine_the_map_outgrew():
+    """A map that outgrew the engine's buffers gets a new engine in profile_phases, as in training_once."""
+    step, kfs, gts = _scaffold(13, False, densify=False)
+    step.training_once(kfs, gts)
+    step.finish()
+    old = step.engine
+    step.model.reserve(6000)
+    need = step.model.capacity * step.model.dims.n_offsets
+    assert old.P < need
+    phases = step.profile_phases(kfs[0], gts[0], iters=2)
+    torch.cuda.synchronize()
+    assert step.engine is not old and step.engine.P >= need
+    assert tuple(phases) == PHASES and all(np.isfinite(v) and v >= 0 for v in phases.values()), phases
+    assert bool(torch.isfinite(step.model.params).all()) and bool(torch.isfinite(step.loss_fn.out[0]))
+
+
 def test_scaffold_graph_survives_adjust_anchor_iterations():
     """adjust_anchor iterations (every 12th here) run eagerly, re-size the model and invalidate the captured graphs; replay
     resumes afterwards with the split anchor / MLP step counts."""
