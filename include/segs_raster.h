@@ -77,6 +77,12 @@ const char* segs_last_error(void);
  * Gaussian instead of only the rows the tile backward added into.  Same gradients (an untouched row converts to zeros); slower
  * wherever much of the scene is occluded.  Steps with and without the flag may alternate on the same buffers. */
 #define SEGS_RASTER_NO_WRITTEN_BYTES 128u
+/* SEGS_RASTER_UNPACKED_BACKWARD (A/B measurements and tests; resident backward entry points): keep the "row written" bytes but
+ * convert the rows with the kernel that gives every one of a workgroup's 256 rows a lane, instead of the packed form, which runs the
+ * projection backward of a workgroup with at most 64 reached rows in one wave (a lane per reached row) while the other waves store
+ * the zeros, and keeps a lane per row only above 64.  Same gradients, bit for bit from the same accumulator rows; slower
+ * wherever much of the scene is occluded.  Steps with and without the flag may alternate on the same buffers. */
+#define SEGS_RASTER_UNPACKED_BACKWARD 256u
 uint32_t segs_raster_set_flags(uint32_t flags);
 
 /* Resident mode only, per host thread; returns the previous pointer.  When set, segs_rasterize_forward_resident also

@@ -353,6 +353,16 @@ int launch_preprocess_bwd(const Gaussians& g, const View& V, const int* radii, c
   auto* const kernel = m.cam ? (depth ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<false, true>)
                              : (depth ? preprocess_bwd_kernel<true, false> : preprocess_bwd_kernel<false, false>);
   const int nblocks = (g.P + 255) / 256;
+  if (m.packed) {   // the resident backward with the bytes (preprocess.hip)
+    auto* const packed = m.cam ? (depth ? preprocess_bwd_packed_kernel<true, true> : preprocess_bwd_packed_kernel<false, true>)
+                               : (depth ? preprocess_bwd_packed_kernel<true, false> : preprocess_bwd_packed_kernel<false, false>);
+    packed<<<nblocks, 256, 0, st>>>(g.P, g.means3D, radii, g.kernel_scales(), g.rotations, g.scale_modifier, g.cov3D_precomp, V.viewmatrix,
+                                    V.projmatrix, V.focal_x, V.focal_y, V.tan_fovx, V.tan_fovy, m.gacc, (float)V.width, (float)V.height,
+                                    o.dL_dmean2D, o.dL_dconic, o.dL_dopacity, o.dL_dcolor, o.dL_dmean3D, o.dL_dcov3D, o.dL_dscale, o.dL_drot,
+                                    m.cam ? camera_partials(m.cam) : nullptr, m.written);
+    LAUNCH_TRY("preprocess_bwd_packed_kernel");
+    return m.cam ? camera_grads_finish(m.cam, nblocks, st) : SEGS_OK;
+  }
   kernel<<<nblocks, 256, 0, st>>>(g.P, g.means3D, radii, g.kernel_scales(), g.rotations, g.scale_modifier, g.cov3D_precomp, V.viewmatrix,
                                   V.projmatrix, V.focal_x, V.focal_y, V.tan_fovx, V.tan_fovy, m.gacc, (float)V.width, (float)V.height,
                                   o.dL_dmean2D, o.dL_dconic, o.dL_dopacity, o.dL_dcolor, o.dL_dmean3D, o.dL_dcov3D, o.dL_dscale, o.dL_drot,
@@ -505,6 +515,7 @@ int rasterize_backward(const Gaussians& g, const View& V, const ScratchBuffers& 
   m.gacc = G.gacc(); m.depth = in.dgrad && in.dgrad->dL_ddepth; m.clean_gacc = self_clean;
   if (cam_live) m.cam = in.cam;
   m.written = (self_clean && !(g_flags & SEGS_RASTER_NO_WRITTEN_BYTES)) ? G.written() : nullptr;
+  m.packed = m.written && !(g_flags & SEGS_RASTER_UNPACKED_BACKWARD);
   if (R > 0)
     if (int rc = launch_render_bwd(S, V, in.background, in.dL_dpix, in.dgrad, m.written, st)) return rc;
   { PROF(K_PREPROCESS_BWD);   // the camera form's second kernel runs inside the same profile slot

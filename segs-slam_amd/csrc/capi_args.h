@@ -150,6 +150,7 @@ struct PerGaussianBwd {
   const float* dz_in = nullptr;    // debug: dL/dz as an input
   const segs_camera_grads* cam = nullptr;   // camera form: + one row of partial sums per workgroup, added up by a second kernel
   uint8_t* written = nullptr;      // the "row written" bytes (gs_layout.h)
+  bool packed = false;             // with the bytes: preprocess_bwd_packed_kernel (a workgroup's reached rows in one wave when they are at most 64)
 };
 
 struct Allocators { segs_alloc_fn geometry_alloc; void* geometry_ctx; segs_alloc_fn binning_alloc; void* binning_ctx; segs_alloc_fn image_alloc; void* image_ctx; };

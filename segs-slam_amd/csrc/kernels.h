@@ -51,6 +51,19 @@ __global__ void preprocess_bwd_kernel(
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int clean_gacc,
     const float* __restrict__ dz_in, float* __restrict__ cam_partials, uint8_t* __restrict__ written);
+// The resident backward with the bytes, packed: a workgroup with at most 64 reached rows runs the arithmetic in ONE wave, a lane per
+// reached row, while its other three waves store the zeros of the rows not reached; with more than 64 every row keeps its lane
+// and the data moves as in preprocess_bwd_kernel.  Always with gacc, written and the write-back of zeros.
+template <bool DEPTH, bool CAM>
+__global__ void preprocess_bwd_packed_kernel(
+    int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,
+    const float* __restrict__ rotations, float mod, const float* __restrict__ cov3D_precomp,
+    const float* __restrict__ view, const float* __restrict__ proj, float h_x, float h_y, float tan_fovx, float tan_fovy,
+    float* __restrict__ gacc, float img_w, float img_h,
+    float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
+    float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
+    float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
+    float* __restrict__ cam_partials, uint8_t* __restrict__ written);
 __global__ void camera_grad_reduce_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ dL_dview,
                                           float* __restrict__ dL_dproj);
 __global__ void sh_backward_kernel(int P, const float* __restrict__ means3D, const int* __restrict__ radii,
