@@ -5,7 +5,7 @@
 //   render_fwd_depth_kernel / render_bwd_depth_kernel: the same two plus a depth map (sum z alpha T) and an alpha map
 //                      (1 - final_T) and their gradients -- template instantiations of the same bodies; no reference counterpart
 //
-// Neither kernel is HBM-bound: per (Gaussian, 8x8 quadrant) the forward issues ~22 vector instructions, the backward ~39,
+// Neither kernel is HBM-bound: per (Gaussian, 8x8 quadrant) the forward issues ~21 vector instructions, the backward ~39,
 // against 64 B of record; the forward is VALU-issue bound, the backward VALU- and LDS-bound at once.
 // MI355X mapping:
 //  * a 16x16 tile (the binning unit, fixed by the reference's key format) is rendered by 4 wave64; each wave owns an 8x8
@@ -18,8 +18,12 @@
 //  * the per-Gaussian operands are wave-uniform: the batch's records are staged in LDS and read as broadcasts
 //    (scalar loads of the records, the first design, were issue- and latency-bound; operands by DPP row broadcast cost as
 //    much VALU issue as the LDS time they save -- both measured).
-//  * early termination is per wave (8x8 block) instead of per 16x16 tile; a terminated pixel keeps T = 0 and a negative
-//    threshold, which makes later Gaussians arithmetic no-ops for it without per-lane branches.
+//  * early termination is per wave (8x8 block) instead of per 16x16 tile, tested once per group of four entries from a lane
+//    mask `live` kept in scalar registers.  A pixel that saturates leaves the mask with T, its sums and its last contributor
+//    as they stood before that Gaussian; from then on the mask zeroes its alpha with the select that the alpha test needs
+//    anyway, so a retired pixel costs one scalar AND per entry and no vector instruction (until round 7 it was kept out by
+//    T = 0 and a negative threshold plus a second copy of T and `last`: five selects, a compare and a ballot on every entry at
+//    which any pixel of the wave saturated -- a third of all entries at 1080p / 3 M).
 //  * exp(power) = exp2(log2e * power) with log2e folded into the stored conic (v_exp_f32).
 //  * backward: two roles alternate inside each wave, 16 list entries at a time (see render_bwd_kernel): pixel lanes
 //    emit w = dL/dG * G and alpha*T into LDS tiles, Gaussian lanes read them transposed and accumulate nine moment sums
@@ -109,11 +113,13 @@ __device__ __forceinline__ void render_fwd_body(
   const uint32_t qbit = 1u << (ID_BITS + wv);
 
   const uint2 range = ranges[tile];
-  // Per-pixel state.  A pixel that has terminated ("dead") keeps T = 0 and thr = -1, which makes every later
-  // Gaussian a no-op for it without any per-lane branch: w = alpha*T = 0 and the stop test T' < thr is false.
-  float T = inside ? 1.0f : 0.f, thr = inside ? 0.0001f : -1.f;
-  float Tfin = 0.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dz = 0.f;
-  uint32_t last = 0u, lastfin = 0u;
+  // Per-pixel state.  `live` is a lane mask in scalar registers: a pixel outside the image never has it, a pixel that saturates
+  // loses it and keeps T, the sums and `last` as they stood BEFORE the Gaussian that saturated it -- which is what the
+  // reference reports as final_T and n_contrib (forward.cu:420-425, 440-447).  No second copy of that state, no threshold
+  // register and no select per state register: retiring a pixel is scalar work on the mask.
+  bool live = inside;
+  float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dz = 0.f;
+  uint32_t last = 0u;
 
   // Software pipeline over 64-entry chunks of the tile list: while chunk c is evaluated, the records of chunk
   // c+1 (gathered one per lane, compacted order) and the list entries of chunk c+2 are in flight.
@@ -158,48 +164,47 @@ __device__ __forceinline__ void render_fwd_body(
     }
     for (int k0 = 0; k0 < n4 && alive; k0 += 4) {
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int k = k0 + u;
-      const float4 q0 = s_rec[wv][k][0], q1 = s_rec[wv][k][1];
-      const float2 q2 = *reinterpret_cast<const float2*>(&s_rec[wv][k][2]);
-      const float qz = DEPTH ? s_rec[wv][k][2].z : 0.f;
-      const float dx = q0.x - pxf, dy = q0.y - pyf;
-      const float power2 = dx * (q0.z * dx + q0.w * dy) + (q1.x * dy) * dy;  // log2e * power
-      const float alpha = fminf(0.99f, q1.y * fast_exp2(power2));
-      const bool ok = power2 <= 0.0f && alpha >= 1.0f / 255.0f;
-      const float ae = ok ? alpha : 0.f;
-      float w = ae * T;
-      float test_T = T - w;
-      const bool stop = test_T < thr;  // forward.cu:420-425; never true for dead pixels (thr = -1)
-      if (__ballot(stop) != 0ull) {    // rare: some pixel saturates at this Gaussian
-        Tfin = stop ? T : Tfin;
-        lastfin = stop ? last : lastfin;   // `last` before this Gaussian: a dead pixel reports lastfin, so the
-        thr = stop ? -1.f : thr;           // unconditional update of `last` below is harmless for it
-        w = stop ? 0.f : w;
-        test_T = stop ? 0.f : test_T;
-        alive = __ballot(thr > 0.f) != 0ull;
+      for (int u = 0; u < 4; u++) {
+        const int k = k0 + u;
+        const float4 q0 = s_rec[wv][k][0], q1 = s_rec[wv][k][1];
+        const float2 q2 = *reinterpret_cast<const float2*>(&s_rec[wv][k][2]);
+        const float qz = DEPTH ? s_rec[wv][k][2].z : 0.f;
+        const float dx = q0.x - pxf, dy = q0.y - pyf;
+        const float power2 = dx * (q0.z * dx + q0.w * dy) + (q1.x * dy) * dy;  // log2e * power
+        const float alpha = fminf(0.99f, q1.y * fast_exp2(power2));
+        // `take`: this pixel takes this Gaussian.  `live` enters here as one scalar AND on the lane mask, and that is all a
+        // retired pixel costs: its alpha becomes 0, so w = 0 and test_T = T, and the stop test below cannot fire again (its
+        // T is still the one from before the Gaussian that saturated it, at least 0.0001).
+        bool take = power2 <= 0.0f && alpha >= 1.0f / 255.0f && live;
+        const float ae = take ? alpha : 0.f;
+        float w = ae * T;
+        float test_T = T - w;
+        const bool stop = test_T < 0.0001f;  // forward.cu:420-425
+        if (__ballot(stop) != 0ull) {        // some pixel saturates at this Gaussian: it leaves the mask and takes nothing of it
+          live = live && !stop;
+          take = take && !stop;
+          w = stop ? 0.f : w;
+          test_T = stop ? T : test_T;
+        }
+        T = test_T;
+        C0 += q1.z * w; C1 += q1.w * w; C2 += q2.x * w;
+        if (DEPTH) Dz += qz * w;
+        last = take ? __float_as_uint(q2.y) : last;
       }
-      T = test_T;
-      C0 += q1.z * w; C1 += q1.w * w; C2 += q2.x * w;
-      if (DEPTH) Dz += qz * w;
-      last = ok ? __float_as_uint(q2.y) : last;
-      if (!alive) break;
-    }
+      alive = __ballot(live) != 0ull;  // once per group: the rest of a group after the last pixel died has no live lane
     }
   }
   if (inside) {
-    const bool dead = thr < 0.f;
     const size_t pix_id = (size_t)W * py + px;
     const size_t HW = (size_t)H * W;
-    const float Tout = dead ? Tfin : T;
-    final_T[pix_id] = Tout;
-    n_contrib[pix_id] = dead ? lastfin : last;
-    out_color[pix_id] = C0 + Tout * bg[0];
-    out_color[HW + pix_id] = C1 + Tout * bg[1];
-    out_color[2 * HW + pix_id] = C2 + Tout * bg[2];
+    final_T[pix_id] = T;
+    n_contrib[pix_id] = last;
+    out_color[pix_id] = C0 + T * bg[0];
+    out_color[HW + pix_id] = C1 + T * bg[1];
+    out_color[2 * HW + pix_id] = C2 + T * bg[2];
     if (DEPTH) {
       if (out_depth) out_depth[pix_id] = Dz;
-      if (out_alpha) out_alpha[pix_id] = 1.0f - Tout;
+      if (out_alpha) out_alpha[pix_id] = 1.0f - T;
     }
   }
 }
