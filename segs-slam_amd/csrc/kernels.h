@@ -40,6 +40,8 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, co
 // CAM: + one row of 24 partial sums of dL/dviewmatrix and dL/dprojmatrix per workgroup into cam_partials (dz_in: see preprocess.hip)
 // written (with gacc; null = every binned row is read): the tile backward's "row written" bytes (gs_layout.h).  Only rows whose
 // byte is set are read, converted and -- with clean_gacc -- cleared together with their bytes; every other row writes zeros.
+// Both kernels below are callers of the same three device functions of preprocess.hip: projection_backward_row (the arithmetic of
+// one binned Gaussian), preprocess_bwd_rows (a row per lane: sweeps, accumulator rows through LDS, stores) and camera_fold.
 constexpr int CAM_SUMS = 24;   // 12 live entries of each 4x4 gradient
 template <bool DEPTH, bool CAM>
 __global__ void preprocess_bwd_kernel(
@@ -53,7 +55,7 @@ __global__ void preprocess_bwd_kernel(
     const float* __restrict__ dz_in, float* __restrict__ cam_partials, uint8_t* __restrict__ written);
 // The resident backward with the bytes, packed: a workgroup with at most 64 reached rows runs the arithmetic in ONE wave, a lane per
 // reached row, while its other three waves store the zeros of the rows not reached; with more than 64 every row keeps its lane
-// and the data moves as in preprocess_bwd_kernel.  Always with gacc, written and the write-back of zeros.
+// and the workgroup runs preprocess_bwd_kernel's body (preprocess_bwd_rows).  Always with gacc, written and the write-back of zeros.
 template <bool DEPTH, bool CAM>
 __global__ void preprocess_bwd_packed_kernel(
     int P, const float* __restrict__ means3D, const int* __restrict__ radii, const float* __restrict__ scales,

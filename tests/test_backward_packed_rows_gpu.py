@@ -2,7 +2,20 @@
 of at most 64 reached rows lists them and one of its waves runs the projection backward while the other three store the zeros of
 the rows not reached; a workgroup with more than 64 keeps a lane per row.  The comparison arm is the same engine under
 SEGS_RASTER_UNPACKED_BACKWARD (the kernel that gives every row a lane, with the bytes), in places also
-SEGS_RASTER_NO_WRITTEN_BYTES; both are the code from before the packed form.
+SEGS_RASTER_NO_WRITTEN_BYTES.  The two kernels are callers of ONE projection backward, ONE lane-per-row body and ONE camera fold
+(projection_backward_row, preprocess_bwd_rows, camera_fold), so the bit-for-bit tests below pin the packing -- list order, the
+slots of the camera fold, the zeros -- and not the arithmetic against a second copy; the arithmetic is held to float64 and to
+the oracle by tests/test_raster_gpu.py, test_camera_grad_gpu.py, test_depth_render_gpu.py and test_backward_written_rows_gpu.py.
+
+Against ANOTHER BUILD of the library (the parent commit's, which cannot be built from a checkout of this one) this module runs as
+a script, once per library:
+    SEGS_RASTER_LIB=/path/to/libsegs_raster.so python -m tests.test_backward_packed_rows_gpu dump a.npz
+    python -m tests.test_backward_packed_rows_gpu dump b.npz && python -m tests.test_backward_packed_rows_gpu compare a.npz b.npz
+The dump holds the raw bits of every gradient tensor of the scenes whose sums have no atomic-order noise (quadrant_case in its four
+forms under flags 0, UNPACKED and NO_WRITTEN_BYTES; blocks_scene under 0 and UNPACKED) and of the stage-alone debug entries on
+the same two scenes, with scales and with cov3D_precomp, plain and in the camera form with dL_dz (the body's path without
+accumulator rows); compare wants every array equal as int32.  profiles/r09_shared_projection_backward.txt records its result
+for the parent of the change that made the three pieces shared.
 
 Scenes, helpers and the noise rule are those of tests/test_backward_written_rows_gpu.py (64x64, at most 2 000 Gaussians): two
 backwards of the same inputs differ by the float atomics of the tile backward, so two arms may differ by ten times the largest
@@ -229,10 +242,11 @@ def quadrant_case():
     return sc, never, touched
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("form", ["plain", "depth", "camera", "cov3D"])
-def test_bit_equality_where_the_sums_are_deterministic(form):
-    sc, never, touched = quadrant_case()
+FORMS = ("plain", "depth", "camera", "cov3D")
+
+
+def form_run(sc, form):
+    """-> (run, step): a resident engine of the form on the 64x64 scene `sc` and step(flags) = one forward + backward of that form."""
     rng = np.random.default_rng(17)
     kw, engine_kw = {}, {}
     if form == "depth":
@@ -243,10 +257,18 @@ def test_bit_equality_where_the_sums_are_deterministic(form):
     run = Run(sc, **engine_kw)
     if form == "cov3D":
         cov = _t(cov3d_of(sc))
-        want, got, want2 = run.step_cov3d(sc, cov, UNPACKED), run.step_cov3d(sc, cov), run.step_cov3d(sc, cov, UNPACKED)
+        return run, lambda flags=0: run.step_cov3d(sc, cov, flags)
+    return run, lambda flags=0: run.step(sc, flags, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", FORMS)
+def test_bit_equality_where_the_sums_are_deterministic(form):
+    sc, never, touched = quadrant_case()
+    run, step = form_run(sc, form)
+    want, got, want2 = step(UNPACKED), step(), step(UNPACKED)
+    if form == "cov3D":
         assert float(got["cov3D"][:512].abs().max()) > 0 and float(got["cov3D"][512:].abs().max()) > 0      # dense and sparse workgroups
-    else:
-        want, got, want2 = run.step(sc, UNPACKED, **kw), run.step(sc, **kw), run.step(sc, UNPACKED, **kw)
     run.resident_and_clean()
     assert_bits_equal(want2, want)      # the premise: this scene's sums do not depend on the order of the atomics
     assert_bits_equal(got, want)
@@ -303,16 +325,22 @@ def test_row_counts_at_wave_and_workgroup_edges(P):
     assert int((run.eng.radii > 0).sum()) > 0
 
 
-@pytest.mark.gpu
-def test_blocks_with_64_65_0_and_256_reached_rows():
+def blocks_scene():
     """Four workgroups of 256 rows: exactly 64 reached rows (the heavy wave full: the last size of the sparse path), 65 (the first
-    of the dense path), none (nothing but zeros), and all 256 (no zeros at all).  Quadrant scene: the arms agree bit for bit."""
+    of the dense path), none (nothing but zeros), and all 256 (no zeros at all)."""
     kinds = []
     for blk, n in enumerate((64, 65, 0, 256)):
         pick = set(np.random.default_rng(blk).permutation(256)[:n].tolist())
         kinds += ["v" if i in pick else "bd"[i % 2] for i in range(256)]
     sc = quadrant_scene(kinds, seed=8)
     sc.opacity[np.array(kinds) == "v"] = 0.1      # seven deep on every quadrant and still all of them contribute
+    return sc
+
+
+@pytest.mark.gpu
+def test_blocks_with_64_65_0_and_256_reached_rows():
+    """blocks_scene() is a quadrant scene: the arms agree bit for bit."""
+    sc = blocks_scene()
     never, touched, _radii = oracle_sets(sc)
     assert [int(touched[256 * b:256 * b + 256].sum()) for b in range(4)] == [64, 65, 0, 256]
     assert not (never & touched).any()
@@ -426,3 +454,63 @@ def test_captured_step_replayed():
         idx = torch.from_numpy(np.flatnonzero(never)).to(DEV)
         for k in TENSORS:
             assert int(torch.count_nonzero(got[k][idx].view(torch.int32))) == 0, k
+
+
+# ------------------------------------------------------------------------------------------- two builds of the library
+FLAG_ARMS = {"0": 0, "UNPACKED": UNPACKED, "NO_WRITTEN_BYTES": NO_WRITTEN_BYTES}
+
+
+def dump(path):
+    """The raw bits of every gradient tensor the loaded library gives on the scenes without atomic-order noise (see the module
+    docstring), and of the stage-alone debug entries, which take the body's path without accumulator rows."""
+    from oracle import gs_oracle
+    from tests.test_camera_grad_gpu import stage
+    out = {}
+
+    def keep(prefix, tensors):
+        for k, v in tensors.items():
+            a = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            out[f"{prefix}/{k}"] = np.ascontiguousarray(a).view(np.int32) if a.dtype == np.float32 else a
+
+    quadrant, blocks = quadrant_case()[0], blocks_scene()
+    for form in FORMS:
+        run, step = form_run(quadrant, form)
+        for arm, flags in FLAG_ARMS.items():
+            keep(f"quadrant/{form}/{arm}", step(flags))
+        run.resident_and_clean()
+    run = Run(blocks)
+    for arm in ("0", "UNPACKED"):
+        keep(f"blocks/{arm}", run.step(blocks, FLAG_ARMS[arm], nan=True))
+    run.resident_and_clean()
+    for name, sc in (("quadrant", quadrant), ("blocks", blocks)):
+        o, g = gs_oracle.run_scene(sc)
+        radii, g2, gc = o.get("radii"), g["dL_dmean2D"], g["dL_dconic"]
+        dz = np.random.default_rng(29).standard_normal(sc.P).astype(np.float32) / 64
+        for pre, cov in (("scales", None), ("cov3D_precomp", cov3d_of(sc))):
+            names = ("mean3D", "cov3D") if cov is not None else ("mean3D", "cov3D", "scale", "rot")
+            grads, _ = stage(sc, radii, g2, gc, cov3D=cov, camera=False)
+            keep(f"stage/{name}/{pre}/plain", dict(zip(names, grads)))
+            grads, mats = stage(sc, radii, g2, gc, dz=dz, cov3D=cov)
+            keep(f"stage/{name}/{pre}/camera_dz", dict(zip(names, grads), view_proj=mats))
+    np.savez(path, **out)
+    print("wrote", len(out), "arrays to", path)
+
+
+def compare(path_a, path_b):
+    a, b = np.load(path_a), np.load(path_b)
+    assert sorted(a.files) == sorted(b.files), sorted(set(a.files) ^ set(b.files))
+    bad = 0
+    for k in sorted(a.files):
+        x, y = a[k], b[k]
+        assert x.dtype == np.int32 and y.dtype == np.int32 and x.shape == y.shape, (k, x.dtype, y.dtype, x.shape, y.shape)
+        if not np.array_equal(x, y):
+            row = int(np.flatnonzero((x != y).reshape(x.shape[0], -1).any(axis=1))[0]) if x.ndim else 0
+            print(f"DIFFERENT: {k}, first at row {row}: {x[row].view(np.float32).tolist()} against {y[row].view(np.float32).tolist()}")
+            bad += 1
+    print(len(a.files), "arrays compared as int32;", "all bit-identical" if not bad else f"{bad} DIFFERENT")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(dump(sys.argv[2]) if sys.argv[1] == "dump" else compare(sys.argv[2], sys.argv[3]))
