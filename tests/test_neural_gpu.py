@@ -484,7 +484,9 @@ def _projecting_pair(case, A, seed, W, H, keep_dead, z_shift=0.0):
 def test_projecting_forward_equals_forward_plus_k1(case, A, size, keep_dead):
     """SURVEY 8f n3 (src/gaussian_renderer.cpp:299-333 -> cuda_rasterizer/forward.cu:155-256): the neural forward that runs the
     rasterizer's per-Gaussian stage itself leaves, bit for bit, what the two separate kernels leave -- candidate geometry, radii,
-    instance counts, image -- and the same gradients (up to the summation order of the tile backward's atomics)."""
+    instance counts, tile ranges, instance values, image -- and the same gradients (up to the summation order of the tile
+    backward's atomics)."""
+    from tests.test_raster_gpu import _capi_state
     a, b, kf, cam = _projecting_pair(case, A, 40 + case, size[0], size[1], keep_dead)
     dL = torch.randn(3, cam.height, cam.width, device="cuda:0") / (3 * cam.height * cam.width)
     for it in range(3):                 # the first render calibrates (unfused on both sides), the others are resident
@@ -497,6 +499,12 @@ def test_projecting_forward_equals_forward_plus_k1(case, A, size, keep_dead):
         assert torch.equal(a.engine.radii[:P], b.engine.radii[:P]), it
         assert torch.equal(a.visible_radii, b.visible_radii), it        # (b's were filled by the projecting forward itself once resident)
         assert (a.engine.R, a.engine.R_live) == (b.engine.R, b.engine.R_live), it
+        if it > 0:      # resident on both sides: the tile ranges and the sorted instance values (index | quadrant mask), bit for bit
+            assert a.engine._last_resident
+            sa, sb = _capi_state(a.engine, cam), _capi_state(b.engine, cam)
+            assert sa["values"].shape[0] == a.engine.R_live
+            for k in ("ranges", "values"):
+                assert np.array_equal(sa[k], sb[k]), (it, k)
         for name in ("means3D", "scales", "rotations", "neural_opacity"):
             xa, xb = getattr(a.neural, name)[:P], getattr(b.neural, name)[:P]
             rows = (a.visible_radii[:a.model.A] > 0).repeat_interleave(10)       # rows of invisible anchors are not written

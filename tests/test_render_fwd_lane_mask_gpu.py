@@ -74,14 +74,17 @@ SCENES = {
 
 
 # ---------------------------------------------------------------------------------------------------------------- engine
-def resident_forward(sc, render_depth=False, colors=None, bg=None):
+def resident_forward(sc, render_depth=False, colors=None, bg=None, keep_dead_instances=False, active=None):
     """Outputs of one resident forward (the second forward of a fresh engine; the first one calibrates through the synchronising
-    path): image, final_T, n_contrib, the tile ranges and instance values the kernel walked, and the depth form's two maps."""
+    path): image, final_T, n_contrib, the tile ranges and instance values the kernel walked, and the depth form's two maps.
+    keep_dead_instances: the engine's switch; active: rasterize only the first `active` rows (RasterEngine.set_active)."""
     import ctypes as C
     from segs_slam_amd import _capi
     from segs_slam_amd.raster_engine import RasterEngine
     cam = sc.camera
-    eng = RasterEngine(sc.P, cam.width, cam.height, DEV, resident=True, render_depth=render_depth)
+    eng = RasterEngine(sc.P, cam.width, cam.height, DEV, resident=True, render_depth=render_depth, keep_dead_instances=keep_dead_instances)
+    if active is not None:
+        eng.set_active(active)
     args = (_t(sc.bg if bg is None else bg), _t(sc.means3D), _t(sc.colors if colors is None else colors), _t(sc.opacity), _t(sc.scales),
             _t(sc.rotations), _t(cam.world_view_transform), _t(cam.full_proj_transform), _t(cam.camera_center), cam.tanfovx, cam.tanfovy)
     eng.forward(*args)
@@ -99,7 +102,8 @@ def resident_forward(sc, render_depth=False, colors=None, bg=None):
     _capi.check(lib.segs_debug_instance_values(p(eng._bin_r), eng.capacity, p(vals), st), "instance_values")
     torch.cuda.synchronize()
     out = dict(out_color=eng.out_color.cpu().numpy(), final_T=final_T.cpu().numpy(), n_contrib=n_contrib.cpu().numpy().view(np.uint32),
-               ranges=ranges.cpu().numpy().astype(np.int64), values=vals.cpu().numpy().view(np.uint32)[:eng.R_live])
+               ranges=ranges.cpu().numpy().astype(np.int64), values=vals.cpu().numpy().view(np.uint32)[:eng.R_live],
+               counts=np.array([eng.R, eng.R_live, eng.R_reference, eng.capacity], dtype=np.int64))      # emitted, live, calibrating call's, capacity
     if render_depth:
         out.update(out_depth=eng.out_depth.cpu().numpy(), out_alpha=eng.out_alpha.cpu().numpy())
     return out
