@@ -62,6 +62,14 @@ class StereoParamsC(C.Structure):
                 ("uniqueness_ratio", C.c_int), ("paths", C.c_int), ("lr_max_diff", C.c_int), ("median", C.c_int)]
 
 
+class IntakeCameraC(C.Structure):
+    """SegsIntakeCamera (include/segs_frame_intake.h)."""
+    _fields_ = [("in_w", C.c_int), ("in_h", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float),
+                ("rinv", C.c_float * 9), ("nfx", C.c_float), ("nfy", C.c_float), ("ncx", C.c_float), ("ncy", C.c_float)]
+
+
 class AdamSegment(C.Structure):
     """segs_adam_segment (include/segs_train.h)."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_double)]
@@ -137,6 +145,11 @@ SYMBOLS.update({
     "segs_stereo_sgm": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     "segs_rgb_to_gray_u8": (_i, [_i, _i, _vp, _vp, _vp]),
     "segs_debug_stereo_sgm_stages": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp] + [_vp] * 6 + [_vp]),
+    "segs_undistort_u8": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "segs_undistort_depth": (_i, [_vp, _i, _vp, _f, _i, _vp, _vp]),
+    "segs_undistort_mask": (_i, [_vp, _vp, _vp]),
+    "segs_debug_undistort_map": (_i, [_vp, _vp, _vp]),
+    "segs_resize_levels": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "segs_l1_ssim_temp_bytes": (_sz, [_i, _i]),
     "segs_l1_ssim_tile_rows": (_i, [_i, _i]),
     "segs_l1_ssim_loss": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
