@@ -11,9 +11,13 @@
 //                            <true> (segs_neural_forward_projected): also runs the rasterizer's per-Gaussian
 //                            stage K1 (project_gaussian.h) on the live candidates and writes its 64-byte records, radii,
 //                            tile counts and depth keys into the resident rasterizer buffers
-//   neural_bwd_kernel      : same mapping; recomputes the forward (cheaper than saving ~100 floats/anchor),
-//                            back-propagates the candidate-domain gradients to anchor/offset/feature/scaling and leaves
-//                            the per-anchor (activation, pre-activation gradient) rows in scratch
+//   neural_bwd_pair_kernel : same mapping; recomputes the forward (cheaper than saving ~100 floats/anchor), back-propagates the
+//                            candidate-domain gradients to anchor/offset/feature/scaling in a chain wave and multiplies the
+//                            MLP weight gradients in its partner wave on the same SIMD; the form every shipped path runs
+//   neural_bwd_kernel      : the one-kernel form of the same backward (SEGS_NEURAL_ONE_KERNEL_BACKWARD): one wave does both.
+//                            The two are callers of one copy of the per-slab gradients and of the write-out ("what the two
+//                            backward kernels share" below); only the feature bank's two small Linears still leave per-anchor
+//                            (activation, pre-activation gradient) rows in scratch
 //   wgrad_mfma_kernel      : dW[j][i] = sum_anchors dpre[a][j] * act[a][i] for all eight Linear layers with
 //                            v_mfma_f32_32x32x2_f32 (exact fp32), operands loaded straight from the scratch rows in
 //                            the MFMA lane order (lane = column, two anchors per instruction); fixed wave count,
@@ -883,13 +887,149 @@ __device__ __forceinline__ void wgrad_chain_tail(const float* bufA, const float*
   }
 }
 
-// End of one MLP in the backward pass: relu mask on dH = W2^T dOUT (accumulated tile by tile), dX (inputs 0..31) on the
-// matrix cores and the view/dist tail on the VALU; dHpre goes to the wave's D tile for the first layer's weight gradient.
-__device__ __forceinline__ void finish_mlp(const float* __restrict__ img, const Small& S, int m, int lane, int h, const f32x16& hpre,
-                                           f32x16& dh, f32x16& dx, float* dtail, float* bufD) {
+// ---- what the two backward kernels share -----------------------------------------------------------------------------------------
+// neural_bwd_kernel (one wave does everything) and neural_bwd_pair_kernel (chain wave + weight-gradient wave) differ in who runs
+// the weight-gradient products, in the length of the dH chain, in the feature-bank epilogue and in where tiles are stored; what a
+// lane computes per anchor and where a workgroup's sums go is the same, and lives here once: the early loads (request_*), the
+// element-wise blocks (output_gradients_*), the end of an MLP (relu_mask, input_gradients), the slab tail (add_scaling_reg,
+// combine_halves, store_scaling_gradient, store_anchor_gradient) and the per-element part of the workgroup epilogue
+// (store_partial_element, store_small_sum, cam_fold, store_cam_row).  The per-anchor gradients of the two forms are bit-identical
+// for the plain model because of it (tests/test_neural_gpu.py).
+
+// Per-lane state of one slab of 32 anchors in a backward chain: the requested inputs and the sums that leave with the slab tail.
+struct SlabLane {
+  float in_op[5], in_col[15];                                    // dL/d(opacity), dL/d(colour) of this half's five candidates
+  float in_sc[6], in_mu[6], in_off[6], in_rot[8], acc_off[6];    // the (up to) two candidates of the current covariance tile
+  float4 acc_feat[4];                                            // the rows the slab's results are added to
+  float acc_scl[6], acc_anc[3];
+  uint32_t keep;                                                 // bit r: candidate 5h + r has neural opacity > 0 (the reference's mask, :279)
+  float reg_acc;                                                 // sum of prod(scaling) over this lane's kept candidates
+  float dgs[6], danc[3];                                         // dL/d(exp(scaling_log)), dL/danchor through xyz
+  float dtail[4];                                                // dL/d(view xyz, dist) (weights are zero where unused)
+};
+__device__ __forceinline__ void slab_begin(SlabLane& s) {
+  s.keep = 0;
+  s.reg_acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < 6; c++) s.dgs[c] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; c++) s.danc[c] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; c++) s.dtail[c] = 0.f;
+}
+// scaling regulariser of the mapper loss, reg_weight * mean_P(prod(scaling)) (src/gaussian_mapper.cpp:926-928):
+// every kept candidate adds reg_weight / P * prod / s_c to dL/dscaling_c
+__device__ __forceinline__ float reg_per_candidate(float reg_weight, const uint32_t* __restrict__ count) {
+  return reg_weight != 0.f ? reg_weight / (float)max(count[1], 1u) : 0.f;
+}
+
+// the five fields of covariance tile `tile`'s (up to) two candidates; masked-out candidates are never read
+__device__ __forceinline__ void request_cov_inputs(int tile, uint32_t c0, const float* g_scales, const float* g_means, const float* offset,
+                                                   const float* g_rot, const float* d_offset, SlabLane& s) {
+#pragma unroll
+  for (int cl = 0; cl < 2; cl++) {
+    const int cc = 2 * (tile - 2) + cl;
+    if (cc < 5 && ((s.keep >> cc) & 1u)) {
+      ldn<3>(g_scales + (c0 + cc) * 3, s.in_sc + 3 * cl);
+      ldn<3>(g_means + (c0 + cc) * 3, s.in_mu + 3 * cl);
+      ldn<3>(offset + (c0 + cc) * 3, s.in_off + 3 * cl);
+      ldn<4>(g_rot + (c0 + cc) * 4, s.in_rot + 4 * cl);
+      ldn<3>(d_offset + (c0 + cc) * 3, s.acc_off + 3 * cl);
+    }
+  }
+}
+__device__ __forceinline__ void request_accumulated_rows(uint32_t a, int h, const float4* dfo, const float* d_scaling_log,
+                                                         const float* d_anchor, SlabLane& s) {
+#pragma unroll
+  for (int g = 0; g < 4; g++) s.acc_feat[g] = dfo[2 * g + h];
+  ldn<6>(d_scaling_log + a * 6, s.acc_scl);
+  ldn<3>(d_anchor + a * 3, s.acc_anc);
+}
+
+// Element-wise: outputs of a tile -> dL/d(output pre-activation), in place (zero for the padding lanes of the last slab: they
+// carry a copy of the last anchor and must not reach the weight gradients).  Tile 0: opacities (tanh) and the keep mask.
+__device__ __forceinline__ void output_gradients_opacity(f32x16& o, bool valid, SlabLane& s) {
+  float d[5];
+#pragma unroll
+  for (int r = 0; r < 5; r++) {
+    const float op = fast_tanh(o[r]);
+    d[r] = 0.f;
+    if (op > 0.f) { s.keep |= 1u << r; d[r] = s.in_op[r] * (1.f - op * op); }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; r++) o[r] = (r < 5 && valid) ? d[r < 5 ? r : 0] : 0.f;
+}
+// tile 1: colours (sigmoid)
+__device__ __forceinline__ void output_gradients_colour(f32x16& o, bool valid, const SlabLane& s) {
+  float d[15];
+#pragma unroll
+  for (int r = 0; r < 15; r++) {
+    const float colv = sigmoidf(o[r]);
+    d[r] = ((s.keep >> (r / 3)) & 1u) ? s.in_col[r] * colv * (1.f - colv) : 0.f;
+  }
+#pragma unroll
+  for (int r = 0; r < 16; r++) o[r] = (r < 15 && valid) ? d[r < 15 ? r : 0] : 0.f;
+}
+// tiles 2..4: scales (sigmoid, with the regulariser), quaternion normalisation; adds this slab's share to d_offset
+__device__ __forceinline__ void output_gradients_cov(f32x16& o, int tile, bool valid, uint32_t c0, const AnchorLane& st, float reg_w,
+                                                     float* d_offset, SlabLane& s) {
+#pragma unroll
+  for (int cl = 0; cl < 2; cl++) {
+    const int cc = 2 * (tile - 2) + cl;
+    const bool on = cc < 5 && ((s.keep >> cc) & 1u);
+    float dsr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float doff[3] = {0.f, 0.f, 0.f};
+    if (on) {
+      const float sr3 = o[7 * cl + 3], sr4 = o[7 * cl + 4], sr5 = o[7 * cl + 5], sr6 = o[7 * cl + 6];
+      float gsc[3] = {s.in_sc[3 * cl], s.in_sc[3 * cl + 1], s.in_sc[3 * cl + 2]};
+      const float gm[3] = {s.in_mu[3 * cl], s.in_mu[3 * cl + 1], s.in_mu[3 * cl + 2]};
+      const float off[3] = {s.in_off[3 * cl], s.in_off[3 * cl + 1], s.in_off[3 * cl + 2]};
+      float sg[3];
+#pragma unroll
+      for (int c = 0; c < 3; c++) sg[c] = sigmoidf(o[7 * cl + c]);
+      if (reg_w != 0.f) {
+        const float s0 = st.gs[3] * sg[0], s1 = st.gs[4] * sg[1], s2 = st.gs[5] * sg[2];
+        gsc[0] += reg_w * (s1 * s2); gsc[1] += reg_w * (s0 * s2); gsc[2] += reg_w * (s0 * s1);
+        s.reg_acc += s0 * s1 * s2;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        s.dgs[3 + c] += gsc[c] * sg[c];
+        dsr[c] = gsc[c] * st.gs[3 + c] * sg[c] * (1.f - sg[c]);
+        s.danc[c] += gm[c];
+        doff[c] = gm[c] * st.gs[c];
+        s.dgs[c] += gm[c] * off[c];
+      }
+      const float4 gr = make_float4(s.in_rot[4 * cl], s.in_rot[4 * cl + 1], s.in_rot[4 * cl + 2], s.in_rot[4 * cl + 3]);
+      const float nr = sqrtf(sr3 * sr3 + sr4 * sr4 + sr5 * sr5 + sr6 * sr6);
+      if (nr >= 1e-12f) {   // r = v / |v|:  dv = (g - r (r.g)) / |v|
+        const float inv = 1.0f / nr;
+        const float r0 = sr3 * inv, r1 = sr4 * inv, r2 = sr5 * inv, r3 = sr6 * inv;
+        const float dot = r0 * gr.x + r1 * gr.y + r2 * gr.z + r3 * gr.w;
+        dsr[3] = (gr.x - r0 * dot) * inv; dsr[4] = (gr.y - r1 * dot) * inv;
+        dsr[5] = (gr.z - r2 * dot) * inv; dsr[6] = (gr.w - r3 * dot) * inv;
+      } else {              // clamp_min(|v|, eps) active: r = v / eps
+        dsr[3] = gr.x * 1e12f; dsr[4] = gr.y * 1e12f; dsr[5] = gr.z * 1e12f; dsr[6] = gr.w * 1e12f;
+      }
+    }
+    if (valid && on) {   // masked-out candidates add nothing
+      const float cur[3] = {s.acc_off[3 * cl] + doff[0], s.acc_off[3 * cl + 1] + doff[1], s.acc_off[3 * cl + 2] + doff[2]};
+      stn<3>(d_offset + (c0 + cc) * 3, cur);
+    }
+#pragma unroll
+    for (int q = 0; q < 7; q++) o[7 * cl + q] = valid ? dsr[q] : 0.f;
+  }
+  o[14] = 0.f; o[15] = 0.f;
+}
+
+// End of one MLP in the backward pass: relu mask on dH = W2^T dOUT (accumulated tile by tile) -- dHpre, which the caller hands to
+// the first layer's weight gradient as a D tile -- then dX (inputs 0..31) on the matrix cores and the view/dist tail on the VALU.
+__device__ __forceinline__ void relu_mask(const f32x16& hpre, f32x16& dh) {
 #pragma unroll
   for (int r = 0; r < 16; r++) dh[r] = hpre[r] > 0.f ? dh[r] : 0.f;
-  put_tile(bufD, lane & 31, h, dh);
+}
+__device__ __forceinline__ void input_gradients(const float* __restrict__ img, const Small& S, int m, int lane, int h, const f32x16& dh,
+                                                f32x16& dx, float* dtail) {
   const float* im = img + (I_DX + m * 16) * 64 + lane;
 #pragma unroll
   for (int s = 0; s < 16; s++) dx = __builtin_amdgcn_mfma_f32_32x32x2f32(im[s * 64], dh[s], dx, 0, 0, 0);
@@ -900,13 +1040,109 @@ __device__ __forceinline__ void finish_mlp(const float* __restrict__ img, const 
   }
 }
 
-// CAM (both backward families): the workgroup also sums  -g_a  over its anchors, g_a = dL/d(anchor - camera centre) through
-// view and dist (the two last terms of dL/danchor below; the xyz = anchor + offset * scaling path does not see the camera).
-// Lane h == 0 of an anchor keeps three accumulators over the workgroup's whole persistent loop; after the loop the lanes of a
-// wave are added by a butterfly, the waves through four LDS slots behind the staging area, both in a fixed order, and the
-// workgroup's row goes to cam_rows[blockIdx.x] with one 16-byte store.  camera_center_reduce_kernel adds the rows that exist.
-// cam_rows is the [BWD_GRID][4] block that follows the partial tiles in the caller's scratch (temp_carve), so the kernels keep
-// their argument list and the plain instantiations (CAM = false) their code.
+// ---- slab tail
+// sum of prod(scaling) over the slab's kept candidates, for the loss value: one float atomic per wave
+__device__ __forceinline__ void add_scaling_reg(float* reg_sum, float reg_w, bool valid, int lane, SlabLane& s) {
+  if (reg_sum != nullptr && reg_w != 0.f) {
+    s.reg_acc = valid ? s.reg_acc : 0.f;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s.reg_acc += __shfl_xor(s.reg_acc, off, 64);
+    if (lane == 0 && s.reg_acc != 0.f) atomicAdd(reg_sum, s.reg_acc);
+  }
+}
+__device__ __forceinline__ void combine_halves(SlabLane& s) {
+#pragma unroll
+  for (int c = 0; c < 6; c++) s.dgs[c] += other_half(s.dgs[c]);
+#pragma unroll
+  for (int c = 0; c < 3; c++) s.danc[c] += other_half(s.danc[c]);
+#pragma unroll
+  for (int c = 0; c < 4; c++) s.dtail[c] += other_half(s.dtail[c]);
+}
+// (late: the accumulated row was not requested with the last tile and is read here)
+__device__ __forceinline__ void store_scaling_gradient(bool late, bool mine, uint32_t a, const AnchorLane& st, float* d_scaling_log,
+                                                       SlabLane& s) {
+  if (mine) {
+    float v[6];
+    if (late) ldn<6>(d_scaling_log + a * 6, s.acc_scl);
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[c] = s.acc_scl[c] + s.dgs[c] * st.gs[c];   // through exp()
+    stn<6>(d_scaling_log + a * 6, v);
+  }
+}
+// view = ob / |ob|, dist = |ob|:  d ob = (dview - view (view . dview)) / dist + ddist * view =: g_a.  CAM: cam[] -= g_a, formed a
+// second time outside the dL/danchor sum, whose bits therefore do not depend on CAM.  On its own g_a is a sum of two
+// products, and contraction may fuse either one: while the kernels each had a copy of this text the compiler rounded the view term
+// first in three of the four CAM instantiations and the dist term first in neural_bwd_kernel<bank, CAM>.  The fused product is
+// now written out, so the choice no longer moves with the surrounding code; DIST_TERM_ROUNDED keeps that one kernel's bits.
+template <bool CAM, bool DIST_TERM_ROUNDED = false>
+__device__ __forceinline__ void store_anchor_gradient(bool late, bool mine, uint32_t a, const AnchorLane& st, float* d_anchor, SlabLane& s,
+                                                      float* cam) {
+  if (mine) {
+    const float* dview = s.dtail;
+    const float vx = st.view[0], vy = st.view[1], vz = st.view[2];
+    const float dot = vx * dview[0] + vy * dview[1] + vz * dview[2];
+    if (late) ldn<3>(d_anchor + a * 3, s.acc_anc);
+    const float v[3] = {s.acc_anc[0] + s.danc[0] + (dview[0] - vx * dot) * st.inv_dist + dview[3] * vx,
+                        s.acc_anc[1] + s.danc[1] + (dview[1] - vy * dot) * st.inv_dist + dview[3] * vy,
+                        s.acc_anc[2] + s.danc[2] + (dview[2] - vz * dot) * st.inv_dist + dview[3] * vz};
+    stn<3>(d_anchor + a * 3, v);
+    if (CAM) {
+      const float view[3] = {vx, vy, vz};
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const float through_view = dview[c] - view[c] * dot;
+        cam[c] -= DIST_TERM_ROUNDED ? __builtin_fmaf(through_view, st.inv_dist, dview[3] * view[c])
+                                    : __builtin_fmaf(dview[3], view[c], through_view * st.inv_dist);
+      }
+    }
+  }
+}
+
+// ---- workgroup epilogue: where the sums of a workgroup go in wgrad_reduce_kernel's partial-tile layout, slot = workgroup
+__device__ __forceinline__ float* partial_slot(float* partial, int job) { return partial + ((size_t)job * WG_WAVES + blockIdx.x) * WG_TILE; }
+// element e = 64 r + lane of accumulator k (0..4: second layer of output tile k, 5..7: first layer of MLP k - 5)
+__device__ __forceinline__ void store_partial_element(float* partial, int k, int e, float sum) {
+  const int r = e >> 6, l = e & 63, i = rho(r, l >> 5), j = l & 31;   // D[i][j]
+  if (k < 5) {            // second layer, tile k: i = tile row -> output unit, j = hidden unit (the Linear's input)
+    const int o = out_row(k, (i >> 2) & 1, (i & 3) + 4 * (i >> 3));
+    if (o >= 0) partial_slot(partial, 3 + tile_mlp(k))[(((o >> 5)) * 32 + j) * 32 + (o & 31)] = sum;
+  } else {                // first layer of MLP k - 5: i = hidden unit, j = feature position 16 (input & 1) + (input >> 1)
+    const int input = 2 * (j & 15) + (j >> 4);
+    partial_slot(partial, k - 5)[(size_t)input * 32 + i] = sum;
+  }
+}
+// small sum q of unit u: sm[] of the kernels
+__device__ __forceinline__ void store_small_sum(float* partial, int q, int u, float sum) {
+  if (q < 5) {              // bias of output tile q: u = tile row
+    const int o = out_row(q, (u >> 2) & 1, (u & 3) + 4 * (u >> 3));
+    if (o >= 0) partial_slot(partial, 3 + tile_mlp(q))[((1 * 3 + (o >> 5)) * 32 + 31) * 32 + (o & 31)] = sum;
+  } else if (q < 8) {       // bias of the hidden layer of MLP q - 5: u = hidden unit
+    partial_slot(partial, q - 5)[((1 * 3 + 0) * 32 + 31) * 32 + u] = sum;
+  } else {                  // tail input 32 + c of MLP (q - 8) / 4
+    const int mm = (q - 8) >> 2, c = (q - 8) & 3;
+    partial_slot(partial, mm)[((1 * 3 + 0) * 32 + c) * 32 + u] = sum;
+  }
+}
+// CAM (both backward kernels): the workgroup also sums  -g_a  over its anchors, g_a = dL/d(anchor - camera centre) through view
+// and dist (store_anchor_gradient; the xyz = anchor + offset * scaling path does not see the camera).  Lane h == 0 of an anchor
+// keeps three accumulators over the workgroup's whole persistent loop; after the loop the lanes of a wave are added by a butterfly
+// (cam_fold), the waves through four LDS slots behind the staging area, both in a fixed order, and the workgroup's row goes to
+// cam_rows[blockIdx.x] with one 16-byte store (store_cam_row).  camera_center_reduce_kernel adds the rows that exist.  cam_rows
+// is the [BWD_GRID][4] block that follows the partial tiles in the caller's scratch (temp_carve), so the kernels keep their
+// argument list and the plain instantiations (CAM = false) their code.
+__device__ __forceinline__ void cam_fold(float* cam, int lane, float* wave_slot) {
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cam[c] += __shfl_xor(cam[c], off, 64);
+    if (lane == 0) wave_slot[c] = cam[c];
+  }
+}
+__device__ __forceinline__ void store_cam_row(const float* cs, float* partial) {   // cs: [4 waves][4]
+  reinterpret_cast<float4*>(partial + PARTIAL_FLOATS)[blockIdx.x] =
+      make_float4((cs[0] + cs[4]) + (cs[8] + cs[12]), (cs[1] + cs[5]) + (cs[9] + cs[13]), (cs[2] + cs[6]) + (cs[10] + cs[14]), 0.f);
+}
+
 template <bool BANK, bool CAM = false>
 __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
     Layout L, const uint32_t* __restrict__ count, const uint32_t* __restrict__ vis, const float* __restrict__ anchor,
@@ -959,54 +1195,27 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
     // the rows the slab's results are added to with the last tile.
     // (The feature-bank variant has no registers to spare for this: it requests each tile's inputs where they are used.)
     constexpr bool EARLY = !BANK;
-    float in_op[5], in_col[15];
-    if (EARLY) { ldn<5>(g_opacity + c0, in_op); ldn<15>(g_colors + c0 * 3, in_col); }
-    float in_sc[6], in_mu[6], in_off[6], in_rot[8], acc_off[6];   // the (up to) two candidates of the current covariance tile
+    SlabLane sl;
+    slab_begin(sl);
+    if (EARLY) { ldn<5>(g_opacity + c0, sl.in_op); ldn<15>(g_colors + c0 * 3, sl.in_col); }
     float4* const dfo = reinterpret_cast<float4*>(d_feat + a * FD);
-    float4 acc_feat[4];
-    float acc_scl[6], acc_anc[3];
     f32x16 dx;
 #pragma unroll
     for (int r = 0; r < 16; r++) dx[r] = 0.f;
-    float dtail[4] = {0.f, 0.f, 0.f, 0.f};
-    uint32_t keep = 0;   // bit r: candidate 5h + r has neural opacity > 0 (the reference's mask, :279)
-    // scaling regulariser of the mapper loss, reg_weight * mean_P(prod(scaling)) (src/gaussian_mapper.cpp:926-928):
-    // every kept candidate adds reg_weight / P * prod / s_c to dL/dscaling_c
-    const float reg_w = reg_weight != 0.f ? reg_weight / (float)max(count[1], 1u) : 0.f;
-    float reg_acc = 0.f;
-    float dgs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, danc[3] = {0.f, 0.f, 0.f};
+    const float reg_w = reg_per_candidate(reg_weight, count);
     f32x16 hp, dh;
 #pragma unroll 1
     for (int tile = 0; tile < N_TILES; tile++) {
       const int m = tile_mlp(tile);
-      auto request_cov_inputs = [&]() {
-#pragma unroll
-        for (int cl = 0; cl < 2; cl++) {
-          const int cc = 2 * (tile - 2) + cl;
-          if (cc < 5 && ((keep >> cc) & 1u)) {   // masked-out candidates are never read
-            ldn<3>(g_scales + (c0 + cc) * 3, in_sc + 3 * cl);
-            ldn<3>(g_means + (c0 + cc) * 3, in_mu + 3 * cl);
-            ldn<3>(offset + (c0 + cc) * 3, in_off + 3 * cl);
-            ldn<4>(g_rot + (c0 + cc) * 4, in_rot + 4 * cl);
-            ldn<3>(d_offset + (c0 + cc) * 3, acc_off + 3 * cl);
-          }
-        }
-      };
-      auto request_accumulated_rows = [&]() {
-#pragma unroll
-        for (int g = 0; g < 4; g++) acc_feat[g] = dfo[2 * g + h];
-        ldn<6>(d_scaling_log + a * 6, acc_scl);
-        ldn<3>(d_anchor + a * 3, acc_anc);
-      };
       if (EARLY && tile >= 2) {
-        request_cov_inputs();
-        if (tile == N_TILES - 1) request_accumulated_rows();
+        request_cov_inputs(tile, c0, g_scales, g_means, offset, g_rot, d_offset, sl);
+        if (tile == N_TILES - 1) request_accumulated_rows(a, h, dfo, d_scaling_log, d_anchor, sl);
       }
       if (!EARLY) {   // nothing is carried from tile to tile: keeps the register allocator from holding these across the loop
 #pragma unroll
-        for (int q = 0; q < 6; q++) { in_sc[q] = 0.f; in_mu[q] = 0.f; in_off[q] = 0.f; acc_off[q] = 0.f; }
+        for (int q = 0; q < 6; q++) { sl.in_sc[q] = 0.f; sl.in_mu[q] = 0.f; sl.in_off[q] = 0.f; sl.acc_off[q] = 0.f; }
 #pragma unroll
-        for (int q = 0; q < 8; q++) in_rot[q] = 0.f;
+        for (int q = 0; q < 8; q++) sl.in_rot[q] = 0.f;
       }
       if (tile <= 2) {
         hp = layer1(img, S, m, lane, h, st.xo);
@@ -1018,77 +1227,15 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
         put_tile(bufH, col, h, hr);
       }
       f32x16 o = layer2(img, S, tile, lane, h, hp);
-      // ---- element-wise: outputs -> dL/d(output pre-activation), in place (zero for the padding lanes of the last slab:
-      // they carry a copy of the last anchor and must not reach the weight gradients)
       if (tile == 0) {
-        float d[5];
-        if (!EARLY) ldn<5>(g_opacity + c0, in_op);
-#pragma unroll
-        for (int r = 0; r < 5; r++) {
-          const float op = fast_tanh(o[r]);
-          d[r] = 0.f;
-          if (op > 0.f) { keep |= 1u << r; d[r] = in_op[r] * (1.f - op * op); }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[r] = (r < 5 && valid) ? d[r < 5 ? r : 0] : 0.f;
+        if (!EARLY) ldn<5>(g_opacity + c0, sl.in_op);
+        output_gradients_opacity(o, valid, sl);
       } else if (tile == 1) {
-        float d[15];
-        if (!EARLY) ldn<15>(g_colors + c0 * 3, in_col);
-#pragma unroll
-        for (int r = 0; r < 15; r++) {
-          const float colv = sigmoidf(o[r]);
-          d[r] = ((keep >> (r / 3)) & 1u) ? in_col[r] * colv * (1.f - colv) : 0.f;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[r] = (r < 15 && valid) ? d[r < 15 ? r : 0] : 0.f;
+        if (!EARLY) ldn<15>(g_colors + c0 * 3, sl.in_col);
+        output_gradients_colour(o, valid, sl);
       } else {
-        if (!EARLY) request_cov_inputs();
-#pragma unroll
-        for (int cl = 0; cl < 2; cl++) {
-          const int cc = 2 * (tile - 2) + cl;
-          const bool on = cc < 5 && ((keep >> cc) & 1u);
-          float dsr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          float doff[3] = {0.f, 0.f, 0.f};
-          if (on) {
-            const float sr3 = o[7 * cl + 3], sr4 = o[7 * cl + 4], sr5 = o[7 * cl + 5], sr6 = o[7 * cl + 6];
-            float gsc[3] = {in_sc[3 * cl], in_sc[3 * cl + 1], in_sc[3 * cl + 2]};
-            const float gm[3] = {in_mu[3 * cl], in_mu[3 * cl + 1], in_mu[3 * cl + 2]};
-            const float off[3] = {in_off[3 * cl], in_off[3 * cl + 1], in_off[3 * cl + 2]};
-            if (reg_w != 0.f) {
-              const float s0 = st.gs[3] * sigmoidf(o[7 * cl]), s1 = st.gs[4] * sigmoidf(o[7 * cl + 1]),
-                          s2 = st.gs[5] * sigmoidf(o[7 * cl + 2]);
-              gsc[0] += reg_w * (s1 * s2); gsc[1] += reg_w * (s0 * s2); gsc[2] += reg_w * (s0 * s1);
-              reg_acc += s0 * s1 * s2;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-              const float sg = sigmoidf(o[7 * cl + c]);
-              dgs[3 + c] += gsc[c] * sg;
-              dsr[c] = gsc[c] * st.gs[3 + c] * sg * (1.f - sg);
-              danc[c] += gm[c];
-              doff[c] = gm[c] * st.gs[c];
-              dgs[c] += gm[c] * off[c];
-            }
-            const float4 gr = make_float4(in_rot[4 * cl], in_rot[4 * cl + 1], in_rot[4 * cl + 2], in_rot[4 * cl + 3]);
-            const float nr = sqrtf(sr3 * sr3 + sr4 * sr4 + sr5 * sr5 + sr6 * sr6);
-            if (nr >= 1e-12f) {   // r = v / |v|:  dv = (g - r (r.g)) / |v|
-              const float inv = 1.0f / nr;
-              const float r0 = sr3 * inv, r1 = sr4 * inv, r2 = sr5 * inv, r3 = sr6 * inv;
-              const float dot = r0 * gr.x + r1 * gr.y + r2 * gr.z + r3 * gr.w;
-              dsr[3] = (gr.x - r0 * dot) * inv; dsr[4] = (gr.y - r1 * dot) * inv;
-              dsr[5] = (gr.z - r2 * dot) * inv; dsr[6] = (gr.w - r3 * dot) * inv;
-            } else {              // clamp_min(|v|, eps) active: r = v / eps
-              dsr[3] = gr.x * 1e12f; dsr[4] = gr.y * 1e12f; dsr[5] = gr.z * 1e12f; dsr[6] = gr.w * 1e12f;
-            }
-          }
-          if (valid && on) {   // masked-out candidates add nothing
-            const float cur[3] = {acc_off[3 * cl] + doff[0], acc_off[3 * cl + 1] + doff[1], acc_off[3 * cl + 2] + doff[2]};
-            stn<3>(d_offset + (c0 + cc) * 3, cur);
-          }
-#pragma unroll
-          for (int q = 0; q < 7; q++) o[7 * cl + q] = valid ? dsr[q] : 0.f;
-        }
-        o[14] = 0.f; o[15] = 0.f;
+        if (!EARLY) request_cov_inputs(tile, c0, g_scales, g_means, offset, g_rot, d_offset, sl);
+        output_gradients_cov(o, tile, valid, c0, st, reg_w, d_offset, sl);
       }
       // ---- second-layer weight gradient of this tile: dOUT tile x H of the MLP
       put_tile(bufD, col, h, o);
@@ -1106,34 +1253,19 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
         for (int s = 0; s < 16; s++) dh = __builtin_amdgcn_mfma_f32_32x32x2f32(im[s * 64], o[s], dh, 0, 0, 0);
       }
       if (tile != 2 && tile != 3) {
-        finish_mlp(img, S, m, lane, h, hp, dh, dx, dtail, bufD);
-          switch (m) {   // first-layer weight gradient: dHpre x (features | tail)
+        relu_mask(hp, dh);
+        put_tile(bufD, col, h, dh);
+        input_gradients(img, S, m, lane, h, dh, dx, sl.dtail);
+        switch (m) {   // first-layer weight gradient: dHpre x (features | tail)
           case 0: wgrad_chain_tail(bufD, bufX, bufT, lane, aW1_0, sm[5], &sm[8]); break;
           case 1: wgrad_chain_tail(bufD, bufX, bufT, lane, aW1_1, sm[6], &sm[12]); break;
           default: wgrad_chain_tail(bufD, bufX, bufT, lane, aW1_2, sm[7], &sm[16]); break;
         }
-        }
+      }
     }
-    if (reg_sum != nullptr && reg_w != 0.f) {   // sum of prod(scaling) over the kept candidates, for the loss value
-      reg_acc = valid ? reg_acc : 0.f;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) reg_acc += __shfl_xor(reg_acc, off, 64);
-      if (lane == 0 && reg_acc != 0.f) atomicAdd(reg_sum, reg_acc);
-    }
-    // ---- combine the lane halves
-#pragma unroll
-    for (int c = 0; c < 6; c++) dgs[c] += other_half(dgs[c]);
-#pragma unroll
-    for (int c = 0; c < 3; c++) danc[c] += other_half(danc[c]);
-#pragma unroll
-    for (int c = 0; c < 4; c++) dtail[c] += other_half(dtail[c]);
-    if (valid && h == 0) {
-      float v[6];
-      if (!EARLY) ldn<6>(d_scaling_log + a * 6, acc_scl);
-#pragma unroll
-      for (int c = 0; c < 6; c++) v[c] = acc_scl[c] + dgs[c] * st.gs[c];   // through exp()
-      stn<6>(d_scaling_log + a * 6, v);
-    }
+    add_scaling_reg(reg_sum, reg_w, valid, lane, sl);
+    combine_halves(sl);
+    store_scaling_gradient(!EARLY, valid && h == 0, a, st, d_scaling_log, sl);
     // dL/dfeat' for all 32 inputs: mine = rows rho(r,h), the other half's = rows rho(r,1-h)
     float dxf[FD];
 #pragma unroll
@@ -1142,7 +1274,6 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
       dxf[rho(r, 0)] = h ? oth : mine;
       dxf[rho(r, 1)] = h ? mine : oth;
     }
-    float dview[4] = {dtail[0], dtail[1], dtail[2], dtail[3]};   // view xyz, dist (weights are zero where unused)
     float df[FD];
     if (BANK) {
       float feat[FD];
@@ -1182,7 +1313,7 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
       }
       if (valid) { stn<FD / 2>(row + R_H + 3 * FD + 16 * h, hfv); stn<FD / 2>(row + R_DH + 3 * FD + 16 * h, dfv); }
 #pragma unroll
-      for (int c = 0; c < 4; c++) dview[c] += dv[c] + other_half(dv[c]);
+      for (int c = 0; c < 4; c++) sl.dtail[c] += dv[c] + other_half(dv[c]);
     } else {
 #pragma unroll
       for (int j = 0; j < FD; j++) df[j] = dxf[j];
@@ -1190,27 +1321,13 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
     if (valid) {   // each half adds its own 16 features: float4 groups 8g + 4h
 #pragma unroll
       for (int g = 0; g < 4; g++) {
-        float4 v = EARLY ? acc_feat[g] : dfo[2 * g + h];
+        float4 v = EARLY ? sl.acc_feat[g] : dfo[2 * g + h];
         v.x += h ? df[8 * g + 4] : df[8 * g]; v.y += h ? df[8 * g + 5] : df[8 * g + 1];
         v.z += h ? df[8 * g + 6] : df[8 * g + 2]; v.w += h ? df[8 * g + 7] : df[8 * g + 3];
         dfo[2 * g + h] = v;
       }
     }
-    // view = ob / |ob|, dist = |ob|:  d ob = (dview - view (view . dview)) / dist + ddist * view
-    if (valid && h == 0) {
-      const float vx = st.view[0], vy = st.view[1], vz = st.view[2];
-      const float dot = vx * dview[0] + vy * dview[1] + vz * dview[2];
-      if (!EARLY) ldn<3>(d_anchor + a * 3, acc_anc);
-      const float v[3] = {acc_anc[0] + danc[0] + (dview[0] - vx * dot) * st.inv_dist + dview[3] * vx,
-                          acc_anc[1] + danc[1] + (dview[1] - vy * dot) * st.inv_dist + dview[3] * vy,
-                          acc_anc[2] + danc[2] + (dview[2] - vz * dot) * st.inv_dist + dview[3] * vz};
-      stn<3>(d_anchor + a * 3, v);
-      if (CAM) {
-        cam[0] -= (dview[0] - vx * dot) * st.inv_dist + dview[3] * vx;
-        cam[1] -= (dview[1] - vy * dot) * st.inv_dist + dview[3] * vy;
-        cam[2] -= (dview[2] - vz * dot) * st.inv_dist + dview[3] * vz;
-      }
-    }
+    store_anchor_gradient<CAM, BANK>(!EARLY, valid && h == 0, a, st, d_anchor, sl, cam);
   }
 
   // ---- the workgroup's weight-gradient partials: the four waves' accumulators summed in a fixed order through LDS (the
@@ -1220,15 +1337,7 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
   constexpr int STAGE = N_SMALL * 64 > 1024 ? N_SMALL * 64 : 1024;
   const int tid = threadIdx.x;
   float* const cam_slot = stage + 4 * STAGE;          // CAM: [4 waves][4] behind the staging area (the barriers below order it)
-  if (CAM) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) cam[c] += __shfl_xor(cam[c], off, 64);
-      if (lane == 0) cam_slot[wv * 4 + c] = cam[c];
-    }
-  }
-  auto slot = [&](int job) { return partial + ((size_t)job * WG_WAVES + blockIdx.x) * WG_TILE; };
+  if (CAM) cam_fold(cam, lane, cam_slot + wv * 4);
 #pragma unroll 1
   for (int k = 0; k < 8; k++) {
     f32x16 v;
@@ -1239,17 +1348,8 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
 #pragma unroll
     for (int r = 0; r < 16; r++) stage[wv * STAGE + r * 64 + lane] = v[r];
     __syncthreads();
-    for (int e = tid; e < 1024; e += 256) {
-      const float sum = (stage[e] + stage[STAGE + e]) + (stage[2 * STAGE + e] + stage[3 * STAGE + e]);
-      const int r = e >> 6, l = e & 63, i = rho(r, l >> 5), j = l & 31;   // D[i][j]
-      if (k < 5) {            // second layer, tile k: i = tile row -> output unit, j = hidden unit (the Linear's input)
-        const int o = out_row(k, (i >> 2) & 1, (i & 3) + 4 * (i >> 3));
-        if (o >= 0) slot(3 + tile_mlp(k))[(((o >> 5)) * 32 + j) * 32 + (o & 31)] = sum;
-      } else {                // first layer of MLP k - 5: i = hidden unit, j = feature position 16 (input & 1) + (input >> 1)
-        const int input = 2 * (j & 15) + (j >> 4);
-        slot(k - 5)[(size_t)input * 32 + i] = sum;
-      }
-    }
+    for (int e = tid; e < 1024; e += 256)
+      store_partial_element(partial, k, e, (stage[e] + stage[STAGE + e]) + (stage[2 * STAGE + e] + stage[3 * STAGE + e]));
     __syncthreads();
   }
 #pragma unroll
@@ -1260,19 +1360,9 @@ __global__ void __launch_bounds__(256, 1) neural_bwd_kernel(
     float sum = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; w++) sum += stage[w * STAGE + q * 64 + u] + stage[w * STAGE + q * 64 + 32 + u];   // both lane halves
-    if (q < 5) {              // bias of output tile q: u = tile row
-      const int o = out_row(q, (u >> 2) & 1, (u & 3) + 4 * (u >> 3));
-      if (o >= 0) slot(3 + tile_mlp(q))[((1 * 3 + (o >> 5)) * 32 + 31) * 32 + (o & 31)] = sum;
-    } else if (q < 8) {       // bias of the hidden layer of MLP q - 5: u = hidden unit
-      slot(q - 5)[((1 * 3 + 0) * 32 + 31) * 32 + u] = sum;
-    } else {                  // tail input 32 + c of MLP (q - 8) / 4
-      const int mm = (q - 8) >> 2, c = (q - 8) & 3;
-      slot(mm)[((1 * 3 + 0) * 32 + c) * 32 + u] = sum;
-    }
+    store_small_sum(partial, q, u, sum);
   }
-  if (CAM && tid == 0)
-    reinterpret_cast<float4*>(partial + PARTIAL_FLOATS)[blockIdx.x] = make_float4((cam_slot[0] + cam_slot[4]) + (cam_slot[8] + cam_slot[12]), (cam_slot[1] + cam_slot[5]) + (cam_slot[9] + cam_slot[13]),
-                                       (cam_slot[2] + cam_slot[6]) + (cam_slot[10] + cam_slot[14]), 0.f);
+  if (CAM && tid == 0) store_cam_row(cam_slot, partial);
 }
 
 // ---- the plain model's backward: chain waves and weight-gradient waves ------------------------------------------------
@@ -1296,8 +1386,11 @@ constexpr int PAIR_STAGE = 8 * 1024 + N_SMALL * 64;   // end of kernel: a wgrad 
 // softmax to the bank's two small Linears 4 -> 32 -> 3; only THEIR weight gradients still go through per-anchor scratch rows
 // (103 of the row's 512 floats) to wgrad_mfma_kernel.  Until round 4 this model ran the one-kernel form: 240 + 91 us at 200 k
 // anchors against 153 us for the plain model's pairs.
-// CAM: see neural_bwd_body.  The chain waves hold the accumulators; their four LDS slots lie behind the wgrad waves' staging
+// CAM: see cam_fold.  The chain waves hold the accumulators; their four LDS slots lie behind the wgrad waves' staging
 // area (the camera launch asks for PAIR_CAM_LDS bytes more), which the operand images and tiles of the run do not reach.
+// What a chain wave computes per anchor and where the workgroup's sums go are the shared helpers above, called in the one-kernel
+// form's order; this kernel's own are the job schedule, the 5 / 15 / 14 / 14 / 7-step dH chain, the placement of the X / T tile
+// stores, the direct dL/dfeat store and the feature-bank epilogue from partial sums.
 constexpr int PAIR_CAM_LDS = 16 * 4;
 template <bool BANK, bool CAM = false>
 __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
@@ -1349,48 +1442,23 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
       float* const row = rows + (valid ? t : 0u) * BROW;
       if (BANK && valid) stn<L1_STEPS>(row + RB_X + L1_STEPS * h, st.xo);   // the feature bank's Linear(4 -> 32) reads view, dist
       const uint32_t c0 = a * NO + 5 * h;   // 32-bit element offsets (the entry points bound A): one SGPR base + one VGPR offset per access
-      float in_op[5], in_col[15];
-      ldn<5>(g_opacity + c0, in_op);
-      ldn<15>(g_colors + c0 * 3, in_col);
-      float in_sc[6], in_mu[6], in_off[6], in_rot[8], acc_off[6];   // the (up to) two candidates of the current covariance tile
+      SlabLane sl;
+      slab_begin(sl);
+      ldn<5>(g_opacity + c0, sl.in_op);
+      ldn<15>(g_colors + c0 * 3, sl.in_col);
       float4* const dfo = reinterpret_cast<float4*>(d_feat + a * FD);
-      float4 acc_feat[4];
-      float acc_scl[6], acc_anc[3];
       f32x16 dx;
 #pragma unroll
       for (int r = 0; r < 16; r++) dx[r] = 0.f;
-      float dtail[4] = {0.f, 0.f, 0.f, 0.f};
-      uint32_t keep = 0;   // bit r: candidate 5h + r has neural opacity > 0 (the reference's mask, :279)
-      // scaling regulariser of the mapper loss, reg_weight * mean_P(prod(scaling)) (src/gaussian_mapper.cpp:926-928):
-      // every kept candidate adds reg_weight / P * prod / s_c to dL/dscaling_c
-      const float reg_w = reg_weight != 0.f ? reg_weight / (float)max(count[1], 1u) : 0.f;
-      float reg_acc = 0.f;
-      float dgs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, danc[3] = {0.f, 0.f, 0.f};
+      const float reg_w = reg_per_candidate(reg_weight, count);
       f32x16 hp, dh;
       int job = 0;   // jobs handed to the wgrad wave in this slab: t0 f0 t1 f2 t2 t3 t4 f1
 #pragma unroll 1
       for (int tile = 0; tile < N_TILES; tile++) {
         const int m = tile_mlp(tile);
-        if (tile >= 2) {
-#pragma unroll
-          for (int cl = 0; cl < 2; cl++) {
-            const int cc = 2 * (tile - 2) + cl;
-            if (cc < 5 && ((keep >> cc) & 1u)) {   // masked-out candidates are never read
-              ldn<3>(g_scales + (c0 + cc) * 3, in_sc + 3 * cl);
-              ldn<3>(g_means + (c0 + cc) * 3, in_mu + 3 * cl);
-              ldn<3>(offset + (c0 + cc) * 3, in_off + 3 * cl);
-              ldn<4>(g_rot + (c0 + cc) * 4, in_rot + 4 * cl);
-              ldn<3>(d_offset + (c0 + cc) * 3, acc_off + 3 * cl);
-            }
-          }
-        }
+        if (tile >= 2) request_cov_inputs(tile, c0, g_scales, g_means, offset, g_rot, d_offset, sl);
         if (tile == 1) a_nx = vis[min(slab_lane(rd + 1), n - 1u)];
-        if (tile == N_TILES - 1) {
-#pragma unroll
-          for (int g = 0; g < 4; g++) acc_feat[g] = dfo[2 * g + h];
-          ldn<6>(d_scaling_log + a * 6, acc_scl);
-          ldn<3>(d_anchor + a * 3, acc_anc);
-        }
+        if (tile == N_TILES - 1) request_accumulated_rows(a, h, dfo, d_scaling_log, d_anchor, sl);
         if (tile <= 2) {
           hp = layer1(img, S, m, lane, h, st.xo);
 #pragma unroll
@@ -1401,76 +1469,9 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
           put_tile(bufH, col, h, hr);   // (the partner is in a first-layer job or idle: it reads D, X, T)
         }
         f32x16 o = layer2(img, S, tile, lane, h, hp);
-        // ---- element-wise: outputs -> dL/d(output pre-activation), in place (zero for the padding lanes of the last slab:
-        // they carry a copy of the last anchor and must not reach the weight gradients)
-        if (tile == 0) {
-          float d[5];
-#pragma unroll
-          for (int r = 0; r < 5; r++) {
-            const float op = fast_tanh(o[r]);
-            d[r] = 0.f;
-            if (op > 0.f) { keep |= 1u << r; d[r] = in_op[r] * (1.f - op * op); }
-          }
-#pragma unroll
-          for (int r = 0; r < 16; r++) o[r] = (r < 5 && valid) ? d[r < 5 ? r : 0] : 0.f;
-        } else if (tile == 1) {
-          float d[15];
-#pragma unroll
-          for (int r = 0; r < 15; r++) {
-            const float colv = sigmoidf(o[r]);
-            d[r] = ((keep >> (r / 3)) & 1u) ? in_col[r] * colv * (1.f - colv) : 0.f;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; r++) o[r] = (r < 15 && valid) ? d[r < 15 ? r : 0] : 0.f;
-        } else {
-#pragma unroll
-          for (int cl = 0; cl < 2; cl++) {
-            const int cc = 2 * (tile - 2) + cl;
-            const bool on = cc < 5 && ((keep >> cc) & 1u);
-            float dsr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            float doff[3] = {0.f, 0.f, 0.f};
-            if (on) {
-              const float sr3 = o[7 * cl + 3], sr4 = o[7 * cl + 4], sr5 = o[7 * cl + 5], sr6 = o[7 * cl + 6];
-              float gsc[3] = {in_sc[3 * cl], in_sc[3 * cl + 1], in_sc[3 * cl + 2]};
-              const float gm[3] = {in_mu[3 * cl], in_mu[3 * cl + 1], in_mu[3 * cl + 2]};
-              const float off[3] = {in_off[3 * cl], in_off[3 * cl + 1], in_off[3 * cl + 2]};
-              float sg[3];
-#pragma unroll
-              for (int c = 0; c < 3; c++) sg[c] = sigmoidf(o[7 * cl + c]);
-              if (reg_w != 0.f) {
-                const float s0 = st.gs[3] * sg[0], s1 = st.gs[4] * sg[1], s2 = st.gs[5] * sg[2];
-                gsc[0] += reg_w * (s1 * s2); gsc[1] += reg_w * (s0 * s2); gsc[2] += reg_w * (s0 * s1);
-                reg_acc += s0 * s1 * s2;
-              }
-#pragma unroll
-              for (int c = 0; c < 3; c++) {
-                dgs[3 + c] += gsc[c] * sg[c];
-                dsr[c] = gsc[c] * st.gs[3 + c] * sg[c] * (1.f - sg[c]);
-                danc[c] += gm[c];
-                doff[c] = gm[c] * st.gs[c];
-                dgs[c] += gm[c] * off[c];
-              }
-              const float4 gr = make_float4(in_rot[4 * cl], in_rot[4 * cl + 1], in_rot[4 * cl + 2], in_rot[4 * cl + 3]);
-              const float nr = sqrtf(sr3 * sr3 + sr4 * sr4 + sr5 * sr5 + sr6 * sr6);
-              if (nr >= 1e-12f) {   // r = v / |v|:  dv = (g - r (r.g)) / |v|
-                const float inv = 1.0f / nr;
-                const float r0 = sr3 * inv, r1 = sr4 * inv, r2 = sr5 * inv, r3 = sr6 * inv;
-                const float dot = r0 * gr.x + r1 * gr.y + r2 * gr.z + r3 * gr.w;
-                dsr[3] = (gr.x - r0 * dot) * inv; dsr[4] = (gr.y - r1 * dot) * inv;
-                dsr[5] = (gr.z - r2 * dot) * inv; dsr[6] = (gr.w - r3 * dot) * inv;
-              } else {              // clamp_min(|v|, eps) active: r = v / eps
-                dsr[3] = gr.x * 1e12f; dsr[4] = gr.y * 1e12f; dsr[5] = gr.z * 1e12f; dsr[6] = gr.w * 1e12f;
-              }
-            }
-            if (valid && on) {   // masked-out candidates add nothing
-              const float cur[3] = {acc_off[3 * cl] + doff[0], acc_off[3 * cl + 1] + doff[1], acc_off[3 * cl + 2] + doff[2]};
-              stn<3>(d_offset + (c0 + cc) * 3, cur);
-            }
-#pragma unroll
-            for (int q = 0; q < 7; q++) o[7 * cl + q] = valid ? dsr[q] : 0.f;
-          }
-          o[14] = 0.f; o[15] = 0.f;
-        }
+        if (tile == 0) output_gradients_opacity(o, valid, sl);
+        else if (tile == 1) output_gradients_colour(o, valid, sl);
+        else output_gradients_cov(o, tile, valid, c0, st, reg_w, d_offset, sl);
         // ---- job "t": dOUT tile x H of the MLP, the partner's
         put_tile((job & 1) ? bufD1 : bufD0, col, h, o);
         __syncthreads();
@@ -1495,45 +1496,21 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
         if (tile != 2 && tile != 3) {
           // end of MLP m: relu mask, job "f" (dHpre x (features | tail)) for the partner, then dX on the matrix cores and the
           // view/dist tail on the VALU
-#pragma unroll
-          for (int r = 0; r < 16; r++) dh[r] = hp[r] > 0.f ? dh[r] : 0.f;
+          relu_mask(hp, dh);
           put_tile((job & 1) ? bufD1 : bufD0, col, h, dh);
           __syncthreads();
           job++;
-          const float* im = img + (I_DX + m * 16) * 64 + lane;
-#pragma unroll
-          for (int s = 0; s < 16; s++) dx = __builtin_amdgcn_mfma_f32_32x32x2f32(im[s * 64], dh[s], dx, 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const float4 w = *reinterpret_cast<const float4*>(S.w1tail[m][rho(r, h)]);
-            dtail[0] += w.x * dh[r]; dtail[1] += w.y * dh[r]; dtail[2] += w.z * dh[r]; dtail[3] += w.w * dh[r];
-          }
+          input_gradients(img, S, m, lane, h, dh, dx, sl.dtail);
         }
       }
-      if (reg_sum != nullptr && reg_w != 0.f) {   // sum of prod(scaling) over the kept candidates, for the loss value
-        reg_acc = valid ? reg_acc : 0.f;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) reg_acc += __shfl_xor(reg_acc, off, 64);
-        if (lane == 0 && reg_acc != 0.f) atomicAdd(reg_sum, reg_acc);
-      }
-      // ---- combine the lane halves
-#pragma unroll
-      for (int c = 0; c < 6; c++) dgs[c] += other_half(dgs[c]);
-#pragma unroll
-      for (int c = 0; c < 3; c++) danc[c] += other_half(danc[c]);
-#pragma unroll
-      for (int c = 0; c < 4; c++) dtail[c] += other_half(dtail[c]);
-      if (valid && h == 0) {
-        float v[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) v[c] = acc_scl[c] + dgs[c] * st.gs[c];   // through exp()
-        stn<6>(d_scaling_log + a * 6, v);
-      }
+      add_scaling_reg(reg_sum, reg_w, valid, lane, sl);
+      combine_halves(sl);
+      store_scaling_gradient(false, valid && h == 0, a, st, d_scaling_log, sl);
       if (!BANK) {
         if (valid) {   // dL/dfeat: each half adds its own 16 features: float4 group 2g + h is rows rho(4g + q, h), this half's registers 4g + q
 #pragma unroll
           for (int g = 0; g < 4; g++) {
-            float4 v = acc_feat[g];
+            float4 v = sl.acc_feat[g];
             v.x += dx[4 * g]; v.y += dx[4 * g + 1]; v.z += dx[4 * g + 2]; v.w += dx[4 * g + 3];
             dfo[2 * g + h] = v;
           }
@@ -1575,7 +1552,7 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
         if (valid) {   // each half adds its own 16 features: float4 groups 2g + h = features 8g + 4h .. + 3
 #pragma unroll
           for (int g = 0; g < 4; g++) {
-            float4 v = acc_feat[g];
+            float4 v = sl.acc_feat[g];
             float add[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
@@ -1615,31 +1592,11 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
           }
         }
 #pragma unroll
-        for (int c = 0; c < 4; c++) dtail[c] += dv[c] + other_half(dv[c]);
+        for (int c = 0; c < 4; c++) sl.dtail[c] += dv[c] + other_half(dv[c]);
       }
-      // view = ob / |ob|, dist = |ob|:  d ob = (dview - view (view . dview)) / dist + ddist * view
-      if (valid && h == 0) {
-        const float vx = st.view[0], vy = st.view[1], vz = st.view[2];
-        const float dot = vx * dtail[0] + vy * dtail[1] + vz * dtail[2];
-        const float v[3] = {acc_anc[0] + danc[0] + (dtail[0] - vx * dot) * st.inv_dist + dtail[3] * vx,
-                            acc_anc[1] + danc[1] + (dtail[1] - vy * dot) * st.inv_dist + dtail[3] * vy,
-                            acc_anc[2] + danc[2] + (dtail[2] - vz * dot) * st.inv_dist + dtail[3] * vz};
-        stn<3>(d_anchor + a * 3, v);
-        if (CAM) {
-          cam[0] -= (dtail[0] - vx * dot) * st.inv_dist + dtail[3] * vx;
-          cam[1] -= (dtail[1] - vy * dot) * st.inv_dist + dtail[3] * vy;
-          cam[2] -= (dtail[2] - vz * dot) * st.inv_dist + dtail[3] * vz;
-        }
-      }
+      store_anchor_gradient<CAM>(false, valid && h == 0, a, st, d_anchor, sl, cam);
     }
-    if (CAM) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cam[c] += __shfl_xor(cam[c], off, 64);
-        if (lane == 0) stage[4 * PAIR_STAGE + pair * 4 + c] = cam[c];
-      }
-    }
+    if (CAM) cam_fold(cam, lane, stage + 4 * PAIR_STAGE + pair * 4);
     __syncthreads();   // every wave is done with the operand images and the tiles
   } else {
     // weight-gradient accumulators: second layers per output tile, first layers per MLP (feature columns)
@@ -1676,38 +1633,17 @@ __global__ void __launch_bounds__(512, 1) neural_bwd_pair_kernel(
   // ---- the workgroup's weight-gradient partials: the four wgrad waves' accumulators summed in a fixed order, written in
   // wgrad_reduce_kernel's partial-tile layout, slot = workgroup
   const int tid = threadIdx.x;
-  auto slot = [&](int job) { return partial + ((size_t)job * WG_WAVES + blockIdx.x) * WG_TILE; };
-  for (int e8 = tid; e8 < 8 * 1024; e8 += 512) {
-    const int k = e8 >> 10, e = e8 & 1023;
-    const float sum = (stage[e8] + stage[PAIR_STAGE + e8]) + (stage[2 * PAIR_STAGE + e8] + stage[3 * PAIR_STAGE + e8]);
-    const int r = e >> 6, l = e & 63, i = rho(r, l >> 5), j = l & 31;   // D[i][j]
-    if (k < 5) {            // second layer, tile k: i = tile row -> output unit, j = hidden unit (the Linear's input)
-      const int o = out_row(k, (i >> 2) & 1, (i & 3) + 4 * (i >> 3));
-      if (o >= 0) slot(3 + tile_mlp(k))[(((o >> 5)) * 32 + j) * 32 + (o & 31)] = sum;
-    } else {                // first layer of MLP k - 5: i = hidden unit, j = feature position 16 (input & 1) + (input >> 1)
-      const int input = 2 * (j & 15) + (j >> 4);
-      slot(k - 5)[(size_t)input * 32 + i] = sum;
-    }
-  }
+  for (int e8 = tid; e8 < 8 * 1024; e8 += 512)
+    store_partial_element(partial, e8 >> 10, e8 & 1023,
+                          (stage[e8] + stage[PAIR_STAGE + e8]) + (stage[2 * PAIR_STAGE + e8] + stage[3 * PAIR_STAGE + e8]));
   for (int e = tid; e < N_SMALL * 32; e += 512) {
     const int q = e >> 5, u = e & 31;
     float sum = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; w++) sum += stage[w * PAIR_STAGE + 8 * 1024 + q * 64 + u] + stage[w * PAIR_STAGE + 8 * 1024 + q * 64 + 32 + u];   // both lane halves
-    if (q < 5) {              // bias of output tile q: u = tile row
-      const int o = out_row(q, (u >> 2) & 1, (u & 3) + 4 * (u >> 3));
-      if (o >= 0) slot(3 + tile_mlp(q))[((1 * 3 + (o >> 5)) * 32 + 31) * 32 + (o & 31)] = sum;
-    } else if (q < 8) {       // bias of the hidden layer of MLP q - 5: u = hidden unit
-      slot(q - 5)[((1 * 3 + 0) * 32 + 31) * 32 + u] = sum;
-    } else {                  // tail input 32 + c of MLP (q - 8) / 4
-      const int mm = (q - 8) >> 2, c = (q - 8) & 3;
-      slot(mm)[((1 * 3 + 0) * 32 + c) * 32 + u] = sum;
-    }
+    store_small_sum(partial, q, u, sum);
   }
-  if (CAM && tid == 0) {
-    const float* const cs = stage + 4 * PAIR_STAGE;
-    reinterpret_cast<float4*>(partial + PARTIAL_FLOATS)[blockIdx.x] = make_float4((cs[0] + cs[4]) + (cs[8] + cs[12]), (cs[1] + cs[5]) + (cs[9] + cs[13]), (cs[2] + cs[6]) + (cs[10] + cs[14]), 0.f);
-  }
+  if (CAM && tid == 0) store_cam_row(stage + 4 * PAIR_STAGE, partial);
 }
 
 // dL/dcamera_center = the sum of the rows the backward's workgroups wrote (cam_rows[w] exists iff workgroup w had a slab, as

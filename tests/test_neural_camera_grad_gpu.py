@@ -110,6 +110,10 @@ def _scattered(n_visible, case):
 # 31 / 33: the slab of 32 anchors; 129: the second workgroup; 32 769: the second round of the 256 persistent workgroups, where an
 # accumulator that does not survive the loop would show.  Case 0: feature bank, case 5: plain; flags 1: the one-kernel family.
 COUNT_PARAMS = [(c, n, 0) for n in (31, 33, 129, 32769) for c in (0, 5)] + [(5, 129, ONE_KERNEL), (0, 129, ONE_KERNEL), (5, 32769, ONE_KERNEL)]
+# Both families at the counts of tests/test_neural_backward_forms_gpu.py: one anchor; 231 of 256 (the second workgroup's last slab
+# has 7 anchors); 32 936 = 32 768 + 128 + 40 (second round: a pair with 8 valid lanes next to two empty pairs, whose lanes carry a
+# copy of the last anchor and must add nothing to the workgroup's row).
+COUNT_PARAMS += [(c, n, f) for n in (1, 231, 32936) for c in (0, 5) for f in (0, ONE_KERNEL)]
 
 
 @pytest.mark.parametrize("case,n_visible,flags", COUNT_PARAMS)
