@@ -153,6 +153,9 @@ SYMBOLS.update({
     "segs_l1_ssim_temp_bytes": (_sz, [_i, _i]),
     "segs_l1_ssim_tile_rows": (_i, [_i, _i]),
     "segs_l1_ssim_loss": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "segs_eval_temp_bytes": (_sz, [_i, _i]),
+    "segs_eval_frame": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "segs_eval_images_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "segs_freq_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "segs_spectrum_magnitude": (_i, [_vp, _sz, _vp, _vp]),
     "segs_freq_temp_bytes": (_sz, [_i, _i, _vp, _vp]),

@@ -20,6 +20,11 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:  # loss_utils.
     return 10.0 * torch.log10(1.0 / mse)
 
 
+def psnr_gaussian_splatting(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:  # loss_utils.h:45-49
+    mse = torch.pow(img1 - img2, 2).view(img1.size(0), -1).mean(1, keepdim=True)
+    return 20.0 * torch.log10(1.0 / torch.sqrt(mse)).mean()
+
+
 def gaussian(window_size: int, sigma: float, device) -> torch.Tensor:  # loss_utils.h:51-64 (INTEGER x = i - 5)
     vals = [math.exp(-float((x - window_size // 2) ** 2) / (2.0 * sigma * sigma)) for x in range(window_size)]
     g = torch.tensor(vals, dtype=torch.float32, device=device)

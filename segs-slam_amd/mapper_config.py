@@ -10,7 +10,8 @@ Mirrors GaussianMapper::readConfigFromFile (src/gaussian_mapper.cpp:224-520): th
     first match.  OpenCV is not installed in this image, so this rule is restated from its source, not executed;
     `duplicates="last"` selects the other reading.
 Only the keys that shape the hot path (model dimensions, optimisation schedule, densification, loss terms) are mapped to
-typed objects; the rest (viewer, recording, SLAM front-end keys) stays available in `MapperConfig.raw`.
+typed objects, and the Record.* keys of the keyframe evaluation (`MapperConfig.record`); the rest (viewer, SLAM front-end
+keys) stays available in `MapperConfig.raw`.
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ from dataclasses import dataclass, field, fields
 from typing import Dict, Optional, Tuple, Union
 
 from .densify import DensifyParams
+from .evaluation import RecordParams
 from .neural_gaussians import ModelDims, ScaffoldOptimizationParams
 
 Scalar = Union[int, float, str]
@@ -80,6 +82,7 @@ class MapperConfig:
     lambda_frequency_low: float = 0.0
     use_coarse_anchor: bool = False
     coarse: Optional["CoarseParams"] = None          # Model.*_coarse / Optimization.*_coarse when use_coarse_anchor (coarse_anchors.py)
+    record: RecordParams = field(default_factory=RecordParams)   # Record.* (evaluation.KeyframeEvaluator)
     raw: Dict[str, Scalar] = field(default_factory=dict)
 
     @property
@@ -136,7 +139,7 @@ def mapper_config_from_values(raw: Dict[str, Scalar], path: str = "<values>") ->
                         frequency_regulization_until=I("Mapper.frequency_regulization_until"),
                         high_frequency_regularization_start=I("Mapper.high_frequency_regularization_start"),
                         lambda_frequency_high=F("Mapper.lambda_frequency_high"), lambda_frequency_low=F("Mapper.lambda_frequency_low"),
-                        use_coarse_anchor=B("Model.use_coarse_anchor"), raw=raw)
+                        use_coarse_anchor=B("Model.use_coarse_anchor"), record=RecordParams.from_config(raw), raw=raw)
 
 
 def load_committed_config(rel_path: str) -> MapperConfig:
